@@ -8,6 +8,13 @@ import os
 import torch
 
 
+def _cpu_env():
+    """Child-process environment with every GPU hidden, for the tests that
+    are about the CPU path (they must also pass on a GPU machine)."""
+    return dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="",
+                ROCR_VISIBLE_DEVICES="")
+
+
 def test_translate_cli_cpu(tmp_path):
     # make a checkpoint with the CPU trainer, then run translate.py on it
     from cyclegan_amd.parallel import DistContext
@@ -56,16 +63,16 @@ def test_main_cli_end_to_end(tmp_path):
            "--num_train_samples", "4", "--num_test_samples", "2",
            "--dtype", "fp32"]
     cwd = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run(cmd, cwd=cwd, capture_output=True, text=True,
-                       timeout=600)
+    r = subprocess.run(cmd, cwd=cwd, env=_cpu_env(), capture_output=True,
+                       text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert os.path.exists(out / "checkpoints" / "checkpoint.pt")
     import glob as g
     assert g.glob(str(out / "events.out.tfevents.*"))
     assert g.glob(str(out / "test" / "events.out.tfevents.*"))
     # auto-resume: second run must report loading the checkpoint
-    r2 = subprocess.run(cmd, cwd=cwd, capture_output=True, text=True,
-                        timeout=600)
+    r2 = subprocess.run(cmd, cwd=cwd, env=_cpu_env(), capture_output=True,
+                        text=True, timeout=600)
     assert r2.returncode == 0, r2.stderr[-2000:]
     assert "restor" in (r2.stdout + r2.stderr).lower() or \
            "resum" in (r2.stdout + r2.stderr).lower() or \
@@ -92,6 +99,37 @@ def test_bench_json_contract(tmp_path):
     assert d["data"] == "synthetic" and d["n_gpus"] == 1
     assert d["value"] > 0 and d["ms_per_step"] > 0
     assert d["config"]["global_batch"] == d["n_gpus"] * d["config"]["per_gpu_batch"]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's ten loss scalars as
+    float32 .npy files; same arguments -> same inputs -> same outputs
+    with or without --full. Runs the deterministic CPU fp32 path (any GPU
+    is hidden from the child) so the outputs can be compared exactly."""
+    import json
+    import numpy as np
+    from cyclegan_amd.trainer import CycleGAN
+    cwd = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = _cpu_env()
+    dumps = []
+    for tag, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / tag
+        r = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", "3",
+             "--warmup", "1", "--output_dir", str(tmp_path),
+             "--dump-outputs", str(d)] + extra,
+            cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = json.loads(r.stdout.strip().splitlines()[-1])
+        assert res["dtype"] == "fp32", "child did not take the CPU path"
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        want = sorted(k.replace("/", "_") + ".npy"
+                      for k in CycleGAN._TRAIN_KEYS)
+        assert sorted(os.listdir(d)) == want
+        dumps.append({f: np.load(d / f) for f in want})
+    for f, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), f
+        np.testing.assert_allclose(a, dumps[1][f], rtol=1e-5, atol=0, err_msg=f)
 
 
 def test_fused_adam_graph_mode_lr_math(tmp_path):
