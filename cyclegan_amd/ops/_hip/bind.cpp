@@ -8,6 +8,14 @@ at::Tensor conv2d_fwd(at::Tensor, at::Tensor, c10::optional<at::Tensor>,
 at::Tensor convt2d_fwd(at::Tensor, at::Tensor, c10::optional<at::Tensor>,
                        int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                        double);
+std::vector<at::Tensor> conv2d_fwd_stats(at::Tensor, at::Tensor,
+                                         c10::optional<at::Tensor>, int64_t,
+                                         int64_t, int64_t, int64_t, int64_t,
+                                         bool, int64_t, double);
+std::vector<at::Tensor> convt2d_fwd_stats(at::Tensor, at::Tensor,
+                                          c10::optional<at::Tensor>, int64_t,
+                                          int64_t, int64_t, int64_t, int64_t,
+                                          int64_t, double);
 at::Tensor conv2d_dgrad(at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
                         int64_t, int64_t, int64_t, int64_t, bool);
 at::Tensor convt2d_dgrad(at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
@@ -27,11 +35,13 @@ at::Tensor conv2d_fp8_fwd(at::Tensor, at::Tensor, at::Tensor,
                           int64_t, int64_t, int64_t, int64_t, int64_t, bool, int64_t, double);
 std::vector<at::Tensor> instnorm_fwd(at::Tensor, at::Tensor, at::Tensor,
                                      double, int64_t, double,
-                                     c10::optional<at::Tensor>);
+                                     c10::optional<at::Tensor>,
+                                     c10::optional<at::Tensor>,
+                                     c10::optional<at::Tensor>, int64_t);
 std::vector<at::Tensor> instnorm_bwd(at::Tensor, at::Tensor, at::Tensor,
                                      at::Tensor, at::Tensor,
                                      c10::optional<at::Tensor>, int64_t,
-                                     double);
+                                     double, c10::optional<at::Tensor>);
 at::Tensor act_bwd(at::Tensor, at::Tensor, int64_t, double);
 at::Tensor channel_sum(at::Tensor);
 at::Tensor reflect_pad_fwd(at::Tensor, int64_t, int64_t, int64_t, int64_t);
@@ -51,6 +61,8 @@ void adam_step(at::Tensor, at::Tensor, at::Tensor, at::Tensor, double, double,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd", &cyg::conv2d_fwd);
   m.def("convt2d_fwd", &cyg::convt2d_fwd);
+  m.def("conv2d_fwd_stats", &cyg::conv2d_fwd_stats);
+  m.def("convt2d_fwd_stats", &cyg::convt2d_fwd_stats);
   m.def("conv2d_dgrad", &cyg::conv2d_dgrad);
   m.def("convt2d_dgrad", &cyg::convt2d_dgrad);
   m.def("conv2d_wgrad", &cyg::conv2d_wgrad);
@@ -63,8 +75,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("quant_fp8_d", &cyg::quant_fp8_d);
   m.def("amax_roll", &cyg::amax_roll);
   m.def("conv2d_fp8_fwd", &cyg::conv2d_fp8_fwd);
-  m.def("instnorm_fwd", &cyg::instnorm_fwd);
-  m.def("instnorm_bwd", &cyg::instnorm_bwd);
+  // trailing optionals keep the short positional forms valid: precomputed
+  // slabs (from conv*_fwd_stats) for fwd, beta (mask recompute) for bwd
+  m.def("instnorm_fwd", &cyg::instnorm_fwd, py::arg("x"), py::arg("gamma"),
+        py::arg("beta"), py::arg("eps"), py::arg("act"), py::arg("slope"),
+        py::arg("residual"), py::arg("psum") = py::none(),
+        py::arg("psq") = py::none(), py::arg("nslabs") = 0);
+  m.def("instnorm_bwd", &cyg::instnorm_bwd, py::arg("dy"), py::arg("x"),
+        py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("yact"),
+        py::arg("act"), py::arg("slope"), py::arg("beta") = py::none());
   m.def("act_bwd", &cyg::act_bwd);
   m.def("channel_sum", &cyg::channel_sum);
   m.def("reflect_pad_fwd", &cyg::reflect_pad_fwd);

@@ -48,6 +48,15 @@ struct ConvParams {
   const float* dqb;              // fp8 delayed-scaling: sw scalar
   long M, KTOT;
   int mtiles, ntiles;
+  // optional InstanceNorm partial slabs written by conv_glds_kernel's
+  // epilogue (null = off): per-(M-tile, channel) sums of the bf16-rounded
+  // outputs and their squares, laid out [(slice*B + b)*Cout + n] with
+  // slice = the tile's index within its sample. tps = M-tiles per sample
+  // (per sample and phase class for the phased convT); the host enables
+  // this only when every tile lies inside one sample.
+  float* psum;
+  float* psq;
+  int tps;
 };
 
 // XCD-aware block remap: hardware dispatches blockIdx round-robin over the
@@ -536,6 +545,9 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
     __syncthreads();  // drains the in-flight glds (vmcnt(0) in the release)
   }
 
+  // per-lane column sums of the stored (bf16-rounded) values and their
+  // squares over this lane's MF*4 rows; lanes past Cout keep zeros
+  float cs[NF] = {}, cq[NF] = {};
   #pragma unroll
   for (int nf = 0; nf < NF; ++nf) {
     int n = n0 + wn0 + nf * 16 + fr;
@@ -555,8 +567,51 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
         }
 #endif
         float v = apply_act(acc[mf][nf][r] + bv, p.act, p.slope);
-        p.y[sm.rowyb[rl] + n] = f2b(v);
+        short hv = f2b(v);
+        p.y[sm.rowyb[rl] + n] = hv;
+        float fv = b2f(hv);
+        cs[nf] += fv;
+        cq[nf] += fv * fv;
       }
+    }
+  }
+
+  // InstanceNorm partial slabs (block-uniform branch). Fixed-order
+  // reduction, no atomics: the four lane>>4 row groups of a wave fold with
+  // two xor shuffles, the NWR waves that share a column meet in LDS, and
+  // one thread per column adds them in wave-row order. The final K-loop
+  // barrier has retired every read of the staging buffers, so A[0]
+  // (16 KiB >= NWR*BNT*2 floats) is free to hold the partials.
+  if (p.psum != nullptr) {
+    float* red = reinterpret_cast<float*>(sm.A[0]);  // [NWR][BNT][2]
+    static_assert(NWR * BNT * 2 * sizeof(float) <= sizeof(sm.A[0]), "red");
+    #pragma unroll
+    for (int nf = 0; nf < NF; ++nf) {
+      float s = cs[nf], q = cq[nf];
+      s += __shfl_xor(s, 16, 64);
+      q += __shfl_xor(q, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      q += __shfl_xor(q, 32, 64);
+      if (fg == 0) {
+        int col = wn0 + nf * 16 + fr;
+        red[(wr * BNT + col) * 2] = s;
+        red[(wr * BNT + col) * 2 + 1] = q;
+      }
+    }
+    __syncthreads();
+    if (tid < BNT && n0 + tid < p.Cout) {
+      float s = 0.f, q = 0.f;
+      #pragma unroll
+      for (int k = 0; k < NWR; ++k) {
+        s += red[(k * BNT + tid) * 2];
+        q += red[(k * BNT + tid) * 2 + 1];
+      }
+      const int mtl = PHASED ? mt - phase * tpp : mt;
+      const int b = mtl / p.tps;
+      const int slice = phase * p.tps + (mtl - b * p.tps);
+      const long o = ((long)slice * p.B + b) * p.Cout + n0 + tid;
+      p.psum[o] = s;
+      p.psq[o] = q;
     }
   }
 }
@@ -1860,15 +1915,56 @@ static void launch_glds_s(const ConvParams& p, dim3 grid, hipStream_t stream) {
   }
 }
 
+// glds path needs 8-aligned channels and 32-bit byte offsets into x and w
+static bool glds_eligible(const ConvParams& p) {
+  return (p.Cin % 8) == 0 &&
+         (long)p.B * p.H * p.W * p.Cin * 2 < (1L << 31) &&
+         (long)p.Cout * p.KTOT * 2 < (1L << 31);
+}
+
+static bool phased_eligible(const ConvParams& p, bool is_convt) {
+  return glds_eligible(p) && is_convt && p.stride == 2 && (p.OH % 2) == 0 &&
+         (p.OW % 2) == 0;
+}
+
+// InstanceNorm slabs from the conv epilogue: number of slabs per sample
+// this call can emit (0 = not eligible; the norm then runs in_reduce).
+// Eligible = conv_glds_kernel runs it with 64/128-wide n-tiles and every
+// 128-row M-tile lies inside one sample: OH*OW % 128 == 0 for the plain
+// row order; for the phased convT the rows of one parity class of one
+// sample are contiguous, so (OH/2)*(OW/2) % 128 == 0 (4 classes per
+// sample). The slab count is capped because every in_norm block re-sums
+// all slabs of its sample in its prologue: HW/128 slabs is a win up to
+// 128^2 (<= today's slice count) and a loss at 256^2 (512 slabs vs 128).
+// CYG_NO_CONV_STATS=1 turns the path off; CYG_CONV_STATS_MAXSLABS moves
+// the cap for A/B runs.
+static int stats_slabs(const ConvParams& p, bool is_convt, int* tps) {
+  static const int cap = []() {
+    const char* off = getenv("CYG_NO_CONV_STATS");
+    if (off && off[0] == '1') return 0;
+    const char* e = getenv("CYG_CONV_STATS_MAXSLABS");
+    return e ? atoi(e) : 128;
+  }();
+  if (cap <= 0 || !glds_eligible(p) || p.Cout <= 16 || (p.Cout % 8) != 0)
+    return 0;
+  long per, ns;
+  if (phased_eligible(p, is_convt)) {
+    per = (long)(p.OH / 2) * (p.OW / 2);
+    ns = 4 * (per / BM);
+  } else {
+    per = (long)p.OH * p.OW;
+    ns = per / BM;
+  }
+  if (per % BM != 0 || ns > cap) return 0;
+  *tps = (int)(per / BM);
+  return (int)ns;
+}
+
 static void launch_conv(const ConvParams& p, bool is_convt, hipStream_t stream) {
   dim3 grid(p.mtiles * p.ntiles);
   bool aligned = (p.Cin % 8) == 0;
-  // glds path needs 32-bit byte offsets into x and w
-  bool glds_ok = aligned &&
-                 (long)p.B * p.H * p.W * p.Cin * 2 < (1L << 31) &&
-                 (long)p.Cout * p.KTOT * 2 < (1L << 31);
-  if (glds_ok && is_convt && p.stride == 2 && (p.OH % 2) == 0 &&
-      (p.OW % 2) == 0) {
+  bool glds_ok = glds_eligible(p);
+  if (phased_eligible(p, is_convt)) {
     // phase-decomposed: 4 phase classes, only matching-parity taps
     ConvParams q = p;
     long Mp = (long)q.B * (q.OH / 2) * (q.OW / 2);
@@ -1928,9 +2024,30 @@ static void check_conv_inputs(const at::Tensor& x, const at::Tensor& w) {
   TORCH_CHECK(w.size(3) == x.size(3), "conv: Cin mismatch");
 }
 
-at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
-                      int64_t stride, int64_t pt, int64_t pb, int64_t pl,
-                      int64_t pr, bool reflect, int64_t act, double slope) {
+// want_stats: also return the InstanceNorm partial slabs {y, psum, psq}
+// ([NS,B,Cout] fp32) when the call is eligible (stats_slabs); {y} otherwise.
+static std::vector<at::Tensor> run_fwd(ConvParams& p, at::Tensor& y,
+                                       bool is_convt, bool want_stats) {
+  std::vector<at::Tensor> out{y};
+  int tps = 0;
+  int ns = want_stats ? stats_slabs(p, is_convt, &tps) : 0;
+  if (ns > 0) {
+    auto ps = at::empty({2, ns, (long)p.B, (long)p.Cout},
+                        y.options().dtype(at::kFloat));
+    p.psum = (float*)ps.mutable_data_ptr();
+    p.psq = p.psum + (long)ns * p.B * p.Cout;
+    p.tps = tps;
+    out.push_back(ps[0]);
+    out.push_back(ps[1]);
+  }
+  launch_conv(p, is_convt, at::cuda::getCurrentCUDAStream());
+  return out;
+}
+
+static std::vector<at::Tensor> conv2d_fwd_impl(
+    at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
+    int64_t stride, int64_t pt, int64_t pb, int64_t pl, int64_t pr,
+    bool reflect, int64_t act, double slope, bool want_stats) {
   check_conv_inputs(x, w);
   int H = x.size(1), W = x.size(2);
   int KH = w.size(1), KW = w.size(2);
@@ -1939,19 +2056,48 @@ at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias
   auto y = at::empty({x.size(0), OH, OW, w.size(0)}, x.options());
   auto p = fill_common(x, w, bias, y, stride, act, slope);
   p.pt = pt; p.pl = pl; p.reflect = reflect ? 1 : 0;
-  launch_conv(p, false, at::cuda::getCurrentCUDAStream());
-  return y;
+  return run_fwd(p, y, false, want_stats);
+}
+
+static std::vector<at::Tensor> convt2d_fwd_impl(
+    at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
+    int64_t stride, int64_t pt, int64_t pl, int64_t out_h, int64_t out_w,
+    int64_t act, double slope, bool want_stats) {
+  check_conv_inputs(x, w);
+  auto y = at::empty({x.size(0), out_h, out_w, w.size(0)}, x.options());
+  auto p = fill_common(x, w, bias, y, stride, act, slope);
+  p.pt = pt; p.pl = pl; p.reflect = 0;
+  return run_fwd(p, y, true, want_stats);
+}
+
+at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
+                      int64_t stride, int64_t pt, int64_t pb, int64_t pl,
+                      int64_t pr, bool reflect, int64_t act, double slope) {
+  return conv2d_fwd_impl(x, w, bias, stride, pt, pb, pl, pr, reflect, act,
+                         slope, false)[0];
+}
+
+std::vector<at::Tensor> conv2d_fwd_stats(
+    at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
+    int64_t stride, int64_t pt, int64_t pb, int64_t pl, int64_t pr,
+    bool reflect, int64_t act, double slope) {
+  return conv2d_fwd_impl(x, w, bias, stride, pt, pb, pl, pr, reflect, act,
+                         slope, true);
 }
 
 at::Tensor convt2d_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
                        int64_t stride, int64_t pt, int64_t pl,
                        int64_t out_h, int64_t out_w, int64_t act, double slope) {
-  check_conv_inputs(x, w);
-  auto y = at::empty({x.size(0), out_h, out_w, w.size(0)}, x.options());
-  auto p = fill_common(x, w, bias, y, stride, act, slope);
-  p.pt = pt; p.pl = pl; p.reflect = 0;
-  launch_conv(p, true, at::cuda::getCurrentCUDAStream());
-  return y;
+  return convt2d_fwd_impl(x, w, bias, stride, pt, pl, out_h, out_w, act,
+                          slope, false)[0];
+}
+
+std::vector<at::Tensor> convt2d_fwd_stats(
+    at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
+    int64_t stride, int64_t pt, int64_t pl, int64_t out_h, int64_t out_w,
+    int64_t act, double slope) {
+  return convt2d_fwd_impl(x, w, bias, stride, pt, pl, out_h, out_w, act,
+                          slope, true);
 }
 
 // conv dgrad: dx = gather-adjoint of conv_fwd == convt kernel on dy with the

@@ -2,10 +2,17 @@
 // pad, per-sample losses, fused TF-Adam — gfx950.
 //
 // InstanceNorm strategy (channels innermost): threads cover whole C-rows
-// with bf16x8 vector loads; per-(b,c) statistics accumulate fp32 via
-// spatial-slice partials + device-scope atomics (grid must outnumber
-// 256 CUs even at batch 1), then a normalize pass fuses affine +
-// activation + residual add. eps = 1e-3 semantics live in Python.
+// with bf16x8 vector loads. Per-(b,c) statistics are fp32 slab partials
+// psum/psq[(slice*B + b)*C + c] with no atomics (run-to-run
+// deterministic): either in_reduce_kernel writes one slab per spatial
+// slice, or the producing conv's epilogue writes one per 128-row M-tile
+// (conv.hip) and in_reduce is skipped. Every block of the normalize pass
+// sums the slabs in its prologue, then fuses affine + activation +
+// residual add. Backward is two passes (slab partials, then dx); the
+// relu/lrelu mask comes from the activated output or, when the caller
+// passes beta instead, from x through the forward's own expression
+// (in_affine).
+// eps = 1e-3 semantics live in Python.
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -137,15 +144,25 @@ __global__ __launch_bounds__(NT) void in_bwd_stats_kernel(
   }
 }
 
+// normalize + affine, pre-activation. ONE definition shared by the forward
+// (in_norm / in_fwd_fused) and by the backward's mask recompute, so both
+// evaluate the same fp32 operations (sub, mul, fma) on the same saved
+// mean/rstd: sign(in_affine) in backward == sign of what forward activated.
+DEV float in_affine(float xv, float m, float rs, float g, float b) {
+  return __fmaf_rn((xv - m) * rs, g, b);
+}
+
 // ---- pass 2 (fused): per-block slab-sum stats + normalize + affine +
-// act (+ residual); slice-0 blocks also persist mean/rstd for backward ----
+// act (+ residual); slice-0 blocks also persist mean/rstd for backward.
+// S slices the grid; NS is the number of slabs to sum (== S after
+// in_reduce, HW/128 when the conv epilogue produced them) ----
 constexpr int MAXC = 2048;
 __global__ __launch_bounds__(NT) void in_norm_kernel(
     const short* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ psum,
     const float* __restrict__ psq, float* __restrict__ mean,
     float* __restrict__ rstd, const short* __restrict__ res,
-    short* __restrict__ y, int B, long HW, int C, int S, int act,
+    short* __restrict__ y, int B, long HW, int C, int S, int NS, int act,
     float slope, float eps) {
   int b = blockIdx.x / S;
   int sl = blockIdx.x % S;
@@ -168,7 +185,7 @@ __global__ __launch_bounds__(NT) void in_norm_kernel(
     for (int c = tid; c < C; c += NT) {
       float sv = 0, qv = 0;
       int k = 0;
-      for (; k + 4 <= S; k += 4) {  // 4 independent chains hide L2 latency
+      for (; k + 4 <= NS; k += 4) {  // 4 independent chains hide L2 latency
         float s0 = psum[((long)(k + 0) * B + b) * C + c];
         float s1 = psum[((long)(k + 1) * B + b) * C + c];
         float s2 = psum[((long)(k + 2) * B + b) * C + c];
@@ -180,7 +197,7 @@ __global__ __launch_bounds__(NT) void in_norm_kernel(
         sv += (s0 + s1) + (s2 + s3);
         qv += (q0 + q1) + (q2 + q3);
       }
-      for (; k < S; ++k) {
+      for (; k < NS; ++k) {
         sv += psum[((long)k * B + b) * C + c];
         qv += psq[((long)k * B + b) * C + c];
       }
@@ -204,7 +221,7 @@ __global__ __launch_bounds__(NT) void in_norm_kernel(
     const int c = tid - kc * C;
     float sv = 0, qv = 0;
     int k = kc;
-    for (; k + 3 * PS < S; k += 4 * PS) {
+    for (; k + 3 * PS < NS; k += 4 * PS) {
       float s0 = psum[((long)(k + 0 * PS) * B + b) * C + c];
       float s1 = psum[((long)(k + 1 * PS) * B + b) * C + c];
       float s2 = psum[((long)(k + 2 * PS) * B + b) * C + c];
@@ -216,7 +233,7 @@ __global__ __launch_bounds__(NT) void in_norm_kernel(
       sv += (s0 + s1) + (s2 + s3);
       qv += (q0 + q1) + (q2 + q3);
     }
-    for (; k < S; k += PS) {
+    for (; k < NS; k += PS) {
       sv += psum[((long)k * B + b) * C + c];
       qv += psq[((long)k * B + b) * C + c];
     }
@@ -257,7 +274,7 @@ __global__ __launch_bounds__(NT) void in_norm_kernel(
       #pragma unroll
       for (int j = 0; j < 8; ++j) {
         int c = g * 8 + j;
-        float val = (b2f(v[j]) - sm[c]) * sr[c] * gamma[c] + beta[c];
+        float val = in_affine(b2f(v[j]), sm[c], sr[c], gamma[c], beta[c]);
         if (res) val += b2f(rv[j]);
         out[j] = f2b(apply_act(val, act, slope));
       }
@@ -267,6 +284,13 @@ __global__ __launch_bounds__(NT) void in_norm_kernel(
 }
 
 // ---- backward pass 1: slab partials of s1 = Σ dy, s2 = Σ dy*xhat ----
+// yy is the activated output when the caller passed yact, else (relu/lrelu
+// only) the recomputed pre-activation in_affine(x): both have the sign the
+// mask needs. tanh needs the output value and always takes yact.
+// The mask source is a template parameter of the backward kernels so the
+// row loops carry no loop-invariant branches (a runtime select there kept
+// the compiler from batching the unrolled loads).
+constexpr int MASK_NONE = 0, MASK_YACT = 1, MASK_X = 2;
 DEV float actbw(float d, float yy, int act, float slope) {
   if (act == ACT_RELU) return yy > 0.f ? d : 0.f;
   if (act == ACT_LRELU) return yy > 0.f ? d : d * slope;
@@ -274,9 +298,11 @@ DEV float actbw(float d, float yy, int act, float slope) {
   return d;
 }
 
+template <int MM>
 __global__ __launch_bounds__(NT) void in_bwd_reduce_kernel(
     const short* __restrict__ dy, const short* __restrict__ x,
-    const short* __restrict__ yact, const float* __restrict__ mean,
+    const short* __restrict__ yact, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ mean,
     const float* __restrict__ rstd,
     float* __restrict__ p1, float* __restrict__ p2, int B, long HW, int C,
     int S, int act, float slope, float* __restrict__ dgb) {
@@ -296,11 +322,15 @@ __global__ __launch_bounds__(NT) void in_bwd_reduce_kernel(
   int rstep = NT / gpr;
   int rof = tid / gpr;
   float a1[8] = {}, a2[8] = {};
-  float mv[8], rv[8];
+  float mv[8], rv[8], gv[8] = {}, bv[8] = {};
   #pragma unroll
   for (int j = 0; j < 8; ++j) {
     mv[j] = mean[(long)b * C + g * 8 + j];
     rv[j] = rstd[(long)b * C + g * 8 + j];
+    if (MM == MASK_X) {
+      gv[j] = gamma[g * 8 + j];
+      bv[j] = beta[g * 8 + j];
+    }
   }
   #pragma unroll 4
   for (long r = r0 + rof; r < r1; r += rstep) {
@@ -308,12 +338,15 @@ __global__ __launch_bounds__(NT) void in_bwd_reduce_kernel(
     v8s dv = *(const v8s*)(dy + off);
     v8s xv = *(const v8s*)(x + off);
     v8s yv = {};
-    if (act != ACT_NONE) yv = *(const v8s*)(yact + off);
+    if (MM == MASK_YACT) yv = *(const v8s*)(yact + off);
     #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float d = b2f(dv[j]);
-      if (act != ACT_NONE) d = actbw(d, b2f(yv[j]), act, slope);
-      float xh = (b2f(xv[j]) - mv[j]) * rv[j];
+      float xf = b2f(xv[j]);
+      if (MM == MASK_YACT) d = actbw(d, b2f(yv[j]), act, slope);
+      if (MM == MASK_X)
+        d = actbw(d, in_affine(xf, mv[j], rv[j], gv[j], bv[j]), act, slope);
+      float xh = (xf - mv[j]) * rv[j];
       a1[j] += d; a2[j] += d * xh;
     }
   }
@@ -339,10 +372,11 @@ __global__ __launch_bounds__(NT) void in_bwd_reduce_kernel(
 
 
 // ---- backward pass 2: dx; also dgamma/dbeta reduce over b ----
+template <int MM>
 __global__ __launch_bounds__(NT) void in_bwd_dx_kernel(
     const short* __restrict__ dy, const short* __restrict__ x,
     const short* __restrict__ yact, const float* __restrict__ gamma,
-    const float* __restrict__ mean,
+    const float* __restrict__ beta, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ p1,
     const float* __restrict__ p2, short* __restrict__ dx,
     float* __restrict__ dbeta, float* __restrict__ dgamma, int B, long HW,
@@ -452,15 +486,19 @@ __global__ __launch_bounds__(NT) void in_bwd_dx_kernel(
       v8s dv = *(const v8s*)(dy + off);
       v8s xv = *(const v8s*)(x + off);
       v8s yv = {};
-      if (act != ACT_NONE) yv = *(const v8s*)(yact + off);
+      if (MM == MASK_YACT) yv = *(const v8s*)(yact + off);
       v8s out;
       #pragma unroll
       for (int j = 0; j < 8; ++j) {
         int c = g * 8 + j;
         float rs = srstd[c];
-        float xh = (b2f(xv[j]) - smean[c]) * rs;
+        float xf = b2f(xv[j]);
+        float xh = (xf - smean[c]) * rs;
         float d = b2f(dv[j]);
-        if (act != ACT_NONE) d = actbw(d, b2f(yv[j]), act, slope);
+        if (MM == MASK_YACT) d = actbw(d, b2f(yv[j]), act, slope);
+        if (MM == MASK_X)
+          d = actbw(d, in_affine(xf, smean[c], rs, gamma[c], beta[c]), act,
+                    slope);
         out[j] = f2b(gamma[c] * rs * (d - sm1[c] - xh * sm2[c]));
       }
       *(v8s*)(dx + off) = out;
@@ -483,9 +521,11 @@ __global__ __launch_bounds__(NT) void in_bwd_dx_kernel(
 typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((address_space(1))) unsigned int gu32;
 
+template <int MM>
 __global__ __launch_bounds__(NT) void in_bwd_fused_kernel(
     const short* __restrict__ dy, const short* __restrict__ x,
     const short* __restrict__ yact, const float* __restrict__ gamma,
+    const float* __restrict__ beta,
     const float* __restrict__ mean, const float* __restrict__ rstd,
     unsigned long long* __restrict__ gq,   // [S*B*C] {p2,p1} pair granules
     unsigned int* __restrict__ arrive,     // [B] counters, zeroed per launch
@@ -506,11 +546,15 @@ __global__ __launch_bounds__(NT) void in_bwd_fused_kernel(
   int rstep = NT / gpr;
   int rof = tid / gpr;
   float a1[8] = {}, a2[8] = {};
-  float mv[8], rv[8];
+  float mv[8], rv[8], gv[8] = {}, bv[8] = {};
   #pragma unroll
   for (int j = 0; j < 8; ++j) {
     mv[j] = mean[(long)b * C + g * 8 + j];
     rv[j] = rstd[(long)b * C + g * 8 + j];
+    if (MM == MASK_X) {
+      gv[j] = gamma[g * 8 + j];
+      bv[j] = beta[g * 8 + j];
+    }
   }
   #pragma unroll 4
   for (long r = r0 + rof; r < r1; r += rstep) {
@@ -518,12 +562,15 @@ __global__ __launch_bounds__(NT) void in_bwd_fused_kernel(
     v8s dv = *(const v8s*)(dy + off);
     v8s xv = *(const v8s*)(x + off);
     v8s yv = {};
-    if (act != ACT_NONE) yv = *(const v8s*)(yact + off);
+    if (MM == MASK_YACT) yv = *(const v8s*)(yact + off);
     #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float d = b2f(dv[j]);
-      if (act != ACT_NONE) d = actbw(d, b2f(yv[j]), act, slope);
-      float xh = (b2f(xv[j]) - mv[j]) * rv[j];
+      float xf = b2f(xv[j]);
+      if (MM == MASK_YACT) d = actbw(d, b2f(yv[j]), act, slope);
+      if (MM == MASK_X)
+        d = actbw(d, in_affine(xf, mv[j], rv[j], gv[j], bv[j]), act, slope);
+      float xh = (xf - mv[j]) * rv[j];
       a1[j] += d; a2[j] += d * xh;
     }
   }
@@ -614,15 +661,19 @@ __global__ __launch_bounds__(NT) void in_bwd_fused_kernel(
     v8s dv = *(const v8s*)(dy + off);
     v8s xv = *(const v8s*)(x + off);
     v8s yv = {};
-    if (act != ACT_NONE) yv = *(const v8s*)(yact + off);
+    if (MM == MASK_YACT) yv = *(const v8s*)(yact + off);
     v8s out;
     #pragma unroll
     for (int j = 0; j < 8; ++j) {
       int c = g * 8 + j;
       float rs = srstd[c];
-      float xh = (b2f(xv[j]) - smean[c]) * rs;
+      float xf = b2f(xv[j]);
+      float xh = (xf - smean[c]) * rs;
       float d = b2f(dv[j]);
-      if (act != ACT_NONE) d = actbw(d, b2f(yv[j]), act, slope);
+      if (MM == MASK_YACT) d = actbw(d, b2f(yv[j]), act, slope);
+      if (MM == MASK_X)
+        d = actbw(d, in_affine(xf, smean[c], rs, gamma[c], beta[c]), act,
+                  slope);
       out[j] = f2b(gamma[c] * rs * (d - sm1[c] - xh * sm2[c]));
     }
     *(v8s*)(dx + off) = out;
@@ -753,7 +804,7 @@ __global__ __launch_bounds__(NT) void in_fwd_fused_kernel(
     #pragma unroll
     for (int j = 0; j < 8; ++j) {
       int c = g * 8 + j;
-      float val = (b2f(v[j]) - sm[c]) * sr[c] * gamma[c] + beta[c];
+      float val = in_affine(b2f(v[j]), sm[c], sr[c], gamma[c], beta[c]);
       if (res) val += b2f(rv[j]);
       out[j] = f2b(apply_act(val, act, slope));
     }
@@ -842,6 +893,30 @@ __global__ void reflect_pad_fwd_kernel(const short* __restrict__ x,
   int ih = mirror_idx(qh - pt, H);
   int iw = mirror_idx(qw - pl, W);
   y[i] = x[(((long)b * H + ih) * W + iw) * C + c];
+}
+
+// C % 8 == 0: one thread copies 8 channels (16 B) of one padded pixel, so
+// the pixel decode runs once per 16 B instead of once per element; IDX is
+// unsigned when the padded tensor has < 2^31 vectors (32-bit div/mod).
+template <typename IDX>
+__global__ __launch_bounds__(256) void reflect_pad_fwd_vec_kernel(
+    const short* __restrict__ x, short* __restrict__ y, int B, int H, int W,
+    int C, int pt, int pb, int pl, int pr) {
+  const int HP = H + pt + pb, WP = W + pl + pr;
+  const IDX gpr = (IDX)(C / 8);
+  const IDX total = (IDX)B * HP * WP * gpr;
+  IDX i = (IDX)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  IDX t = i / gpr;
+  int g = (int)(i - t * gpr);
+  IDX t2 = t / (IDX)WP;
+  int qw = (int)(t - t2 * WP);
+  IDX b = t2 / (IDX)HP;
+  int qh = (int)(t2 - b * HP);
+  int ih = mirror_idx(qh - pt, H);
+  int iw = mirror_idx(qw - pl, W);
+  long src = (((long)b * H + ih) * W + iw) * C + g * 8;
+  *(v8s*)(y + (long)i * 8) = *(const v8s*)(x + src);
 }
 
 __global__ void reflect_pad_bwd_kernel(const short* __restrict__ dyp,
@@ -991,7 +1066,10 @@ static int slices_for(long HW, int B) {
 std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
                                      at::Tensor beta, double eps, int64_t act,
                                      double slope,
-                                     c10::optional<at::Tensor> residual) {
+                                     c10::optional<at::Tensor> residual,
+                                     c10::optional<at::Tensor> psum_in,
+                                     c10::optional<at::Tensor> psq_in,
+                                     int64_t nslabs) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous());
   int B = x.size(0), C = x.size(3);
   long HW = (long)x.size(1) * x.size(2);
@@ -1005,6 +1083,30 @@ std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
   auto y = at::empty_like(x);
   const short* resf = residual.has_value()
                           ? (const short*)residual->const_data_ptr() : nullptr;
+
+  if (psum_in.has_value()) {
+    // slabs precomputed by the producing conv's epilogue ([nslabs,B,C]
+    // fp32, one per 128-row M-tile): no in_reduce pass. The grid keeps
+    // slices_for(); only the prologue's slab count changes.
+    TORCH_CHECK(psq_in.has_value() && nslabs >= 1 &&
+                psum_in->scalar_type() == at::kFloat &&
+                psq_in->scalar_type() == at::kFloat &&
+                psum_in->is_contiguous() && psq_in->is_contiguous() &&
+                psum_in->numel() == nslabs * B * C &&
+                psq_in->numel() == nslabs * B * C,
+                "instnorm_fwd: bad precomputed slabs");
+    hipLaunchKernelGGL(in_norm_kernel, dim3(B * S), dim3(NT), 0, stream,
+                       (const short*)x.const_data_ptr(),
+                       (const float*)gamma.const_data_ptr(),
+                       (const float*)beta.const_data_ptr(),
+                       (const float*)psum_in->const_data_ptr(),
+                       (const float*)psq_in->const_data_ptr(),
+                       (float*)mean.mutable_data_ptr(),
+                       (float*)rstd.mutable_data_ptr(), resf,
+                       (short*)y.mutable_data_ptr(), B, HW, C, S,
+                       (int)nslabs, (int)act, (float)slope, (float)eps);
+    return {y, mean, rstd};
+  }
 
   static int fused_cap = []() {
     // measured NEGATIVE at bench shapes (288 vs 314 img/s): the
@@ -1070,8 +1172,8 @@ std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
                        (const float*)beta.const_data_ptr(), nullptr, nullptr,
                        (float*)mean.mutable_data_ptr(),
                        (float*)rstd.mutable_data_ptr(), res,
-                       (short*)y.mutable_data_ptr(), B, HW, C, S, (int)act,
-                       (float)slope, (float)eps);
+                       (short*)y.mutable_data_ptr(), B, HW, C, S, S,
+                       (int)act, (float)slope, (float)eps);
     return {y, mean, rstd};
   }
   hipLaunchKernelGGL(in_norm_kernel, dim3(B * S), dim3(NT), 0, stream,
@@ -1082,18 +1184,45 @@ std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
                      (const float*)psq.const_data_ptr(),
                      (float*)mean.mutable_data_ptr(),
                      (float*)rstd.mutable_data_ptr(), res,
-                     (short*)y.mutable_data_ptr(), B, HW, C, S, (int)act,
-                     (float)slope, (float)eps);
+                     (short*)y.mutable_data_ptr(), B, HW, C, S, S,
+                     (int)act, (float)slope, (float)eps);
   return {y, mean, rstd};
 }
+
+// launch a backward kernel template with the mask mode chosen at run time
+#define LAUNCH_MM(kern, mm, grid, stream, ...)                              \
+  do {                                                                      \
+    if ((mm) == MASK_X)                                                     \
+      hipLaunchKernelGGL(kern<MASK_X>, grid, dim3(NT), 0, stream,           \
+                         __VA_ARGS__);                                      \
+    else if ((mm) == MASK_YACT)                                             \
+      hipLaunchKernelGGL(kern<MASK_YACT>, grid, dim3(NT), 0, stream,        \
+                         __VA_ARGS__);                                      \
+    else                                                                    \
+      hipLaunchKernelGGL(kern<MASK_NONE>, grid, dim3(NT), 0, stream,        \
+                         __VA_ARGS__);                                      \
+  } while (0)
 
 std::vector<at::Tensor> instnorm_bwd(at::Tensor dy, at::Tensor x,
                                      at::Tensor gamma, at::Tensor mean,
                                      at::Tensor rstd,
                                      c10::optional<at::Tensor> yact,
-                                     int64_t act, double slope) {
+                                     int64_t act, double slope,
+                                     c10::optional<at::Tensor> beta) {
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 &&
               dy.is_contiguous() && x.is_contiguous());
+  // without yact the relu/lrelu mask is recomputed from x, which needs
+  // beta; tanh needs the output value itself
+  TORCH_CHECK(act == ACT_NONE || yact.has_value() ||
+              ((act == ACT_RELU || act == ACT_LRELU) && beta.has_value()),
+              "instnorm_bwd: act ", act, " needs yact (or beta for relu/lrelu)");
+  TORCH_CHECK(!beta.has_value() ||
+              (beta->scalar_type() == at::kFloat && beta->numel() == x.size(3)),
+              "instnorm_bwd: beta must be fp32 [C]");
+  const float* betap =
+      beta.has_value() ? (const float*)beta->const_data_ptr() : nullptr;
+  const int mm = act == ACT_NONE ? MASK_NONE
+                                 : (yact.has_value() ? MASK_YACT : MASK_X);
   int B = x.size(0), C = x.size(3);
   long HW = (long)x.size(1) * x.size(2);
   TORCH_CHECK(C % 8 == 0 && (C / 8) <= 256 && 256 % std::min(C / 8, 256) == 0,
@@ -1120,7 +1249,8 @@ std::vector<at::Tensor> instnorm_bwd(at::Tensor dy, at::Tensor x,
     int bpc = 0, ncu = 0, dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &bpc, (const void*)in_bwd_fused_kernel, NT, 0) != hipSuccess)
+            &bpc, (const void*)in_bwd_fused_kernel<MASK_YACT>, NT, 0) !=
+        hipSuccess)
       return 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount,
                               dev) != hipSuccess)
@@ -1136,10 +1266,10 @@ std::vector<at::Tensor> instnorm_bwd(at::Tensor dy, at::Tensor x,
                              stream));
     CHECK_HIP(hipMemsetAsync(dgb.mutable_data_ptr(), 0,
                              (size_t)2 * C * 4, stream));
-    hipLaunchKernelGGL(in_bwd_fused_kernel, dim3(B * Sf), dim3(NT), 0,
+    LAUNCH_MM(in_bwd_fused_kernel, mm, dim3(B * Sf),
                        stream, (const short*)dy.const_data_ptr(),
                        (const short*)x.const_data_ptr(), yp,
-                       (const float*)gamma.const_data_ptr(),
+                       (const float*)gamma.const_data_ptr(), betap,
                        (const float*)mean.const_data_ptr(),
                        (const float*)rstd.const_data_ptr(),
                        (unsigned long long*)gq.mutable_data_ptr(),
@@ -1153,9 +1283,10 @@ std::vector<at::Tensor> instnorm_bwd(at::Tensor dy, at::Tensor x,
 
   auto p1 = at::empty({S, B, C}, fopt);
   auto p2 = at::empty({S, B, C}, fopt);
-  hipLaunchKernelGGL(in_bwd_reduce_kernel, dim3(B * S), dim3(NT), 0, stream,
+  LAUNCH_MM(in_bwd_reduce_kernel, mm, dim3(B * S), stream,
                      (const short*)dy.const_data_ptr(),
                      (const short*)x.const_data_ptr(), yp,
+                     (const float*)gamma.const_data_ptr(), betap,
                      (const float*)mean.const_data_ptr(),
                      (const float*)rstd.const_data_ptr(),
                      (float*)p1.mutable_data_ptr(),
@@ -1178,10 +1309,10 @@ std::vector<at::Tensor> instnorm_bwd(at::Tensor dy, at::Tensor x,
                        (float*)s2m.mutable_data_ptr(),
                        (float*)dbeta.mutable_data_ptr(),
                        (float*)dgamma.mutable_data_ptr(), B, HW, C, S);
-    hipLaunchKernelGGL(in_bwd_dx_kernel, dim3(B * S), dim3(NT), 0, stream,
+    LAUNCH_MM(in_bwd_dx_kernel, mm, dim3(B * S), stream,
                        (const short*)dy.const_data_ptr(),
                        (const short*)x.const_data_ptr(), yp,
-                       (const float*)gamma.const_data_ptr(),
+                       (const float*)gamma.const_data_ptr(), betap,
                        (const float*)mean.const_data_ptr(),
                        (const float*)rstd.const_data_ptr(),
                        (const float*)s1m.const_data_ptr(),
@@ -1192,10 +1323,10 @@ std::vector<at::Tensor> instnorm_bwd(at::Tensor dy, at::Tensor x,
                        (int)act, (float)slope);
     return {dx, dgamma, dbeta};
   }
-  hipLaunchKernelGGL(in_bwd_dx_kernel, dim3(B * S), dim3(NT), 0, stream,
+  LAUNCH_MM(in_bwd_dx_kernel, mm, dim3(B * S), stream,
                      (const short*)dy.const_data_ptr(),
                      (const short*)x.const_data_ptr(), yp,
-                     (const float*)gamma.const_data_ptr(),
+                     (const float*)gamma.const_data_ptr(), betap,
                      (const float*)mean.const_data_ptr(),
                      (const float*)rstd.const_data_ptr(),
                      (const float*)p1.const_data_ptr(),
@@ -1244,6 +1375,34 @@ at::Tensor reflect_pad_fwd(at::Tensor x, int64_t pt, int64_t pb, int64_t pl,
   int B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   auto y = at::empty({B, H + pt + pb, W + pl + pr, C}, x.options());
   long total = y.numel();
+  TORCH_CHECK(pt >= 0 && pb >= 0 && pl >= 0 && pr >= 0 && pt < H && pb < H &&
+              pl < W && pr < W, "reflect_pad: pads must be in [0, size)");
+  // CYG_NO_PAD_VEC=1 restores the one-element-per-thread kernel everywhere
+  static const bool no_vec = []() {
+    const char* e = getenv("CYG_NO_PAD_VEC");
+    return e && e[0] == '1';
+  }();
+  const bool al16 = ((uintptr_t)x.const_data_ptr() % 16) == 0 &&
+                    ((uintptr_t)y.const_data_ptr() % 16) == 0;
+  if (!no_vec && C % 8 == 0 && al16 && total > 0) {
+    long nvec = total / 8;
+    TORCH_CHECK((nvec + 255) / 256 < (1L << 31), "reflect_pad: too large");
+    dim3 grid((unsigned)((nvec + 255) / 256));
+    if (nvec < (1L << 31) - 256) {
+      hipLaunchKernelGGL(reflect_pad_fwd_vec_kernel<unsigned>, grid,
+                         dim3(256), 0, at::cuda::getCurrentCUDAStream(),
+                         (const short*)x.const_data_ptr(),
+                         (short*)y.mutable_data_ptr(), B, H, W, C, (int)pt,
+                         (int)pb, (int)pl, (int)pr);
+    } else {
+      hipLaunchKernelGGL(reflect_pad_fwd_vec_kernel<unsigned long>, grid,
+                         dim3(256), 0, at::cuda::getCurrentCUDAStream(),
+                         (const short*)x.const_data_ptr(),
+                         (short*)y.mutable_data_ptr(), B, H, W, C, (int)pt,
+                         (int)pb, (int)pl, (int)pr);
+    }
+    return y;
+  }
   hipLaunchKernelGGL(reflect_pad_fwd_kernel, dim3(cdiv64(total, 256)),
                      dim3(256), 0, at::cuda::getCurrentCUDAStream(),
                      (const short*)x.const_data_ptr(),

@@ -95,6 +95,29 @@ def _convt_ref(x, w, bias, stride, pt, pl, out_h, out_w):
     return y.permute(0, 2, 3, 1)
 
 
+# Attribute under which a conv output carries the InstanceNorm partial
+# slabs its epilogue produced: (psum, psq), each [NS, B, C] fp32,
+# non-differentiable. ops.norm.instance_norm picks them up when the shapes
+# match and then skips its own reduce pass. Only bias-free, activation-free
+# bf16 HIP convs emit them (in these models: exactly the convs followed by
+# IN), and only when the kernel library finds the shape eligible.
+IN_SLABS_ATTR = "_cyg_in_slabs"
+
+
+def _want_stats(bias, act) -> bool:
+    return bias is None and act == ACT_NONE
+
+
+def _attach_slabs(out):
+    """Unpack a Function result that may carry slabs: (y, psum, psq) -> y
+    with the slabs attached; a bare tensor passes through."""
+    if isinstance(out, tuple):
+        y, psum, psq = out
+        setattr(y, IN_SLABS_ATTR, (psum, psq))
+        return y
+    return out
+
+
 def _pad_channels(t: torch.Tensor, c_to: int = 8) -> torch.Tensor:
     """Zero-pad the channel (last) dim of an NHWC tensor up to c_to."""
     c = t.shape[-1]
@@ -118,16 +141,28 @@ class _ConvFn(torch.autograd.Function):
         xp = _pad_channels(x).contiguous()
         wc = compute_weight_p(w, x)
         bc = compute_bias_p(bias, x) if bias is not None else None
-        y = ext.conv2d_fwd(xp, wc, bc, stride, *pads, reflect, act, slope)
+        slabs = ()
+        if _want_stats(bias, act) and cout >= 8:
+            y, *slabs = ext.conv2d_fwd_stats(xp, wc, bc, stride, *pads,
+                                             reflect, act, slope)
+        else:
+            y = ext.conv2d_fwd(xp, wc, bc, stride, *pads, reflect, act, slope)
         if cout < 8:
             y = y[..., :cout].contiguous()
         ctx.save_for_backward(xp, w, y)
         ctx.conf = (stride, pads, reflect, act, slope, bias is not None,
                     x.shape[3])
+        if slabs:
+            # no zero-filled grads for the slab outputs in backward
+            ctx.set_materialize_grads(False)
+            ctx.mark_non_differentiable(*slabs)
+            return (y, *slabs)
         return y
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, *_):
+        if dy is None:  # only with set_materialize_grads(False): y unused
+            return (None,) * 8
         xp, w, y = ctx.saved_tensors
         stride, pads, reflect, act, slope, has_bias, cin = ctx.conf
         cout = w.shape[0]
@@ -285,13 +320,26 @@ class _ConvTFn(torch.autograd.Function):
         ext = backend.ext()
         wc = compute_weight(w, x)
         bc = compute_weight(bias, x) if bias is not None else None
-        y = ext.convt2d_fwd(x, wc, bc, stride, pt, pl, out_h, out_w, act, slope)
+        slabs = ()
+        if _want_stats(bias, act):
+            y, *slabs = ext.convt2d_fwd_stats(x, wc, bc, stride, pt, pl,
+                                              out_h, out_w, act, slope)
+        else:
+            y = ext.convt2d_fwd(x, wc, bc, stride, pt, pl, out_h, out_w, act,
+                                slope)
         ctx.save_for_backward(x, w, y)
         ctx.conf = (stride, pt, pl, act, slope, bias is not None)
+        if slabs:
+            # no zero-filled grads for the slab outputs in backward
+            ctx.set_materialize_grads(False)
+            ctx.mark_non_differentiable(*slabs)
+            return (y, *slabs)
         return y
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, *_):
+        if dy is None:  # only with set_materialize_grads(False): y unused
+            return (None,) * 10
         x, w, y = ctx.saved_tensors
         stride, pt, pl, act, slope, has_bias = ctx.conf
         ext = backend.ext()
@@ -353,7 +401,8 @@ def conv2d(
                      or w.shape[1] == 4)):
             return _ConvFp8Fn.apply(x, w, bias, stride, pads,
                                     pad_mode == "reflect", a, slope)
-        return _ConvFn.apply(x, w, bias, stride, pads, pad_mode == "reflect", a, slope)
+        return _attach_slabs(_ConvFn.apply(x, w, bias, stride, pads,
+                                           pad_mode == "reflect", a, slope))
     wc = w if w.dtype == x.dtype else w.to(x.dtype)
     bc = bias if (bias is None or bias.dtype == x.dtype) else bias.to(x.dtype)
     y = _conv_ref(x, wc, bc, stride, pads, pad_mode)
@@ -378,7 +427,8 @@ def conv_transpose2d(
     pt, _, pl, _ = same_pads(out_h, out_w, kh, kw, stride)
     a = _ACT[act]
     if backend.use_hip(x, w):
-        return _ConvTFn.apply(x, w, bias, stride, pt, pl, out_h, out_w, a, slope)
+        return _attach_slabs(_ConvTFn.apply(x, w, bias, stride, pt, pl, out_h,
+                                            out_w, a, slope))
     wc = w if w.dtype == x.dtype else w.to(x.dtype)
     bc = bias if (bias is None or bias.dtype == x.dtype) else bias.to(x.dtype)
     y = _convt_ref(x, wc, bc, stride, pt, pl, out_h, out_w)
