@@ -34,7 +34,12 @@ class Discriminator(nn.Module):
         self.head = ConvNHWC(f, 1, 4, 1, padding="same", bias=True)
 
     def forward(self, x):
+        # fp8 hand-off hints (ops.instance_norm): every norm names the conv
+        # that reads it; only the 256- and 512-channel norms in front of
+        # the two stride-1 convs pass the fp8 dispatch predicate.
         h = self.stem(x)
-        for m in self.mids:
-            h = m(h)
+        n = len(self.mids)
+        for i in range(0, n, 2):
+            nxt = self.mids[i + 2] if i + 2 < n else self.head
+            h = self.mids[i + 1](self.mids[i](h), fp8_consumer=nxt.fp8_hint())
         return self.head(h)

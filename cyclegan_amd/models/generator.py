@@ -49,11 +49,20 @@ class Generator(nn.Module):
                              init="glorot")
 
     def forward(self, x):
+        # fp8 hand-off hints (ops.instance_norm): each norm whose output
+        # feeds a resblock conv is told which conv that is — the last down
+        # norm -> blocks[0].conv1, block i -> block i+1's conv1; the last
+        # block feeds a transpose conv and gets none.
+        nb = len(self.blocks)
         h = self.stem_norm(self.stem_conv(x))
-        for m in self.downs:
-            h = m(h)
-        for b in self.blocks:
-            h = b(h)
+        for i, m in enumerate(self.downs):
+            if nb and i == len(self.downs) - 1:
+                h = m(h, fp8_consumer=self.blocks[0].conv1.fp8_hint())
+            else:
+                h = m(h)
+        for i, b in enumerate(self.blocks):
+            nxt = self.blocks[i + 1].conv1.fp8_hint() if i + 1 < nb else None
+            h = b(h, fp8_consumer=nxt)
         for m in self.ups:
             h = m(h)
         return self.head(h)

@@ -52,6 +52,11 @@ class ConvNHWC(nn.Module):
         return ops.conv2d(x, self.weight, self.bias, self.stride,
                           self.padding, self.pad_mode, self.act, self.slope)
 
+    def fp8_hint(self) -> ops.Fp8Consumer:
+        """What the norm producing this conv's input needs to know to hand
+        it an fp8 operand (ops.instance_norm's ``fp8_consumer``)."""
+        return ops.Fp8Consumer(self.weight, self.stride)
+
 
 class ConvTransposeNHWC(nn.Module):
     """TF-'SAME' stride-s transpose conv: out = in * stride."""
@@ -84,9 +89,11 @@ class InstanceNormNHWC(nn.Module):
         self.gamma = nn.Parameter(torch.empty(channels).normal_(0.0, 0.02))
         self.beta = nn.Parameter(torch.zeros(channels))
 
-    def forward(self, x, residual: Optional[torch.Tensor] = None):
+    def forward(self, x, residual: Optional[torch.Tensor] = None,
+                fp8_consumer: Optional[ops.Fp8Consumer] = None):
         return ops.instance_norm(x, self.gamma, self.beta, self.eps,
-                                 self.act, self.slope, residual)
+                                 self.act, self.slope, residual,
+                                 fp8_consumer=fp8_consumer)
 
 
 class ResBlock(nn.Module):
@@ -104,6 +111,9 @@ class ResBlock(nn.Module):
                               padding=(1, 1, 1, 1), pad_mode="reflect")
         self.norm2 = InstanceNormNHWC(channels)
 
-    def forward(self, x):
-        h = self.norm1(self.conv1(x))
-        return self.norm2(self.conv2(h), residual=x)
+    def forward(self, x, fp8_consumer: Optional[ops.Fp8Consumer] = None):
+        """``fp8_consumer``: the conv that reads this block's output (the
+        next block's conv1), for norm2's fp8 hand-off."""
+        h = self.norm1(self.conv1(x), fp8_consumer=self.conv2.fp8_hint())
+        return self.norm2(self.conv2(h), residual=x,
+                          fp8_consumer=fp8_consumer)

@@ -33,11 +33,21 @@ void amax_roll(at::Tensor, int64_t);
 at::Tensor conv2d_fp8_fwd(at::Tensor, at::Tensor, at::Tensor,
                           c10::optional<at::Tensor>, c10::optional<at::Tensor>,
                           int64_t, int64_t, int64_t, int64_t, int64_t, bool, int64_t, double);
+std::vector<at::Tensor> conv2d_fp8_fwd_stats(
+    at::Tensor, at::Tensor, at::Tensor, c10::optional<at::Tensor>,
+    c10::optional<at::Tensor>, int64_t, int64_t, int64_t, int64_t, int64_t,
+    bool, int64_t, double);
 std::vector<at::Tensor> instnorm_fwd(at::Tensor, at::Tensor, at::Tensor,
                                      double, int64_t, double,
                                      c10::optional<at::Tensor>,
                                      c10::optional<at::Tensor>,
                                      c10::optional<at::Tensor>, int64_t);
+std::vector<at::Tensor> instnorm_fwd_q8(at::Tensor, at::Tensor, at::Tensor,
+                                        double, int64_t, double,
+                                        c10::optional<at::Tensor>,
+                                        c10::optional<at::Tensor>,
+                                        c10::optional<at::Tensor>, int64_t,
+                                        at::Tensor, at::Tensor);
 std::vector<at::Tensor> instnorm_bwd(at::Tensor, at::Tensor, at::Tensor,
                                      at::Tensor, at::Tensor,
                                      c10::optional<at::Tensor>, int64_t,
@@ -75,12 +85,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("quant_fp8_d", &cyg::quant_fp8_d);
   m.def("amax_roll", &cyg::amax_roll);
   m.def("conv2d_fp8_fwd", &cyg::conv2d_fp8_fwd);
+  m.def("conv2d_fp8_fwd_stats", &cyg::conv2d_fp8_fwd_stats);
   // trailing optionals keep the short positional forms valid: precomputed
   // slabs (from conv*_fwd_stats) for fwd, beta (mask recompute) for bwd
   m.def("instnorm_fwd", &cyg::instnorm_fwd, py::arg("x"), py::arg("gamma"),
         py::arg("beta"), py::arg("eps"), py::arg("act"), py::arg("slope"),
         py::arg("residual"), py::arg("psum") = py::none(),
         py::arg("psq") = py::none(), py::arg("nslabs") = 0);
+  // instnorm_fwd + the e4m3 twin of y for the consuming fp8 conv (slabs
+  // are positional here: pass None, None, 0 for the in_reduce route)
+  m.def("instnorm_fwd_q8", &cyg::instnorm_fwd_q8, py::arg("x"),
+        py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("act"),
+        py::arg("slope"), py::arg("residual"), py::arg("psum"),
+        py::arg("psq"), py::arg("nslabs"), py::arg("amax_prev"),
+        py::arg("amax_cur"));
   m.def("instnorm_bwd", &cyg::instnorm_bwd, py::arg("dy"), py::arg("x"),
         py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("yact"),
         py::arg("act"), py::arg("slope"), py::arg("beta") = py::none());

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
+#include <hip/hip_fp8.h>
 
 #define DEV __device__ __forceinline__
 
@@ -23,6 +24,22 @@ DEV float b2f(short raw) {
 DEV short f2b(float f) {
   __hip_bfloat16 h = __float2bfloat16(f);  // RNE
   return *reinterpret_cast<short*>(&h);
+}
+
+// ---- fp8 (OCP e4m3) delayed-scaling quantisation ----
+// ONE definition of the scale and of the conversion, shared by the
+// standalone quant kernels and the conv epilogue (conv.hip) and by the
+// InstanceNorm kernel that emits its consumer's fp8 operand
+// (norm_elem.hip): identical inputs give identical bytes everywhere.
+// sx comes from the PREVIOUS step's amax (persistent per-layer slot).
+DEV float delayed_sx(float amax_prev) {
+  return fminf(448.f / fmaxf(amax_prev, 1e-12f), 65504.f);
+}
+
+// e4m3 byte of f * s (fp32 product, saturating RNE conversion)
+DEV unsigned char f2e4m3(float f, float s) {
+  __hip_fp8_e4m3 q(f * s);
+  return q.__x;
 }
 
 // activation codes shared with python (ops/conv.py)

@@ -773,8 +773,6 @@ __global__ __launch_bounds__(NW * 64) void conv_halo_kernel(ConvParams p) {
 // 4 mfma_f32_16x16x32_fp8_fp8 substeps. Forward only: backward reuses the
 // bf16 kernels from the saved bf16 activations (master-grad numerics).
 
-#include <hip/hip_fp8.h>
-
 constexpr int BKF = 128;  // fp8 K-step (elements == bytes)
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
@@ -798,14 +796,12 @@ __global__ void quant_fp8_kernel(const short* __restrict__ x,
     unsigned char out[8];
     #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      __hip_fp8_e4m3 q(b2f(v[j]) * s);
-      out[j] = q.__x;
+      out[j] = f2e4m3(b2f(v[j]), s);
     }
     *(uint2*)(y + i) = *(uint2*)out;
   } else if (i < n) {
     for (long k = i; k < n; ++k) {
-      __hip_fp8_e4m3 q(b2f(x[k]) * scale[0]);
-      y[k] = q.__x;
+      y[k] = f2e4m3(b2f(x[k]), scale[0]);
     }
   }
 }
@@ -815,10 +811,8 @@ __global__ void quant_fp8_kernel(const short* __restrict__ x,
 // transformer-engine style) so no separate full-tensor reduction runs
 // before quantization; this call's max|x| block-reduces and atomically
 // maxes into the CURRENT slot (nonneg float bits order == value order),
-// rolled once per step by amax_roll.
-DEV float delayed_sx(float amax_prev) {
-  return fminf(448.f / fmaxf(amax_prev, 1e-12f), 65504.f);
-}
+// rolled once per step by amax_roll. delayed_sx and the e4m3 conversion
+// live in common.h.
 
 __global__ __launch_bounds__(256) void quant_fp8_d_kernel(
     const short* __restrict__ x, const float* __restrict__ amax_prev,
@@ -838,8 +832,7 @@ __global__ __launch_bounds__(256) void quant_fp8_d_kernel(
     for (int j = 0; j < 8; ++j) {
       float f = b2f(v[j]);
       mx = fmaxf(mx, fabsf(f));
-      __hip_fp8_e4m3 q(f * s);
-      out[j] = q.__x;
+      out[j] = f2e4m3(f, s);
     }
     *(uint2*)(y + i) = *(uint2*)out;
   }
@@ -848,8 +841,7 @@ __global__ __launch_bounds__(256) void quant_fp8_d_kernel(
     for (long k = n & ~7L; k < n; ++k) {
       float f = b2f(x[k]);
       mx = fmaxf(mx, fabsf(f));
-      __hip_fp8_e4m3 q(f * s);
-      y[k] = q.__x;
+      y[k] = f2e4m3(f, s);
     }
   }
   __shared__ float red[256];
@@ -872,7 +864,10 @@ __global__ void amax_roll_kernel(float* __restrict__ arena, int n, int cap) {
   }
 }
 
-template <int STRIDE>
+// STATS: also emit the InstanceNorm partial slabs (p.psum/p.psq/p.tps as
+// in conv_glds_kernel). A template parameter, so the plain instantiation
+// carries neither the extra accumulators nor the branch.
+template <int STRIDE, bool STATS>
 __global__ __launch_bounds__(NTHREADS) void conv_fp8_kernel(ConvParams p) {
   const int stride = STRIDE ? STRIDE : p.stride;
   __shared__ Fp8Smem sm;
@@ -1062,6 +1057,9 @@ __global__ __launch_bounds__(NTHREADS) void conv_fp8_kernel(ConvParams p) {
   const float dqs = p.dq
       ? (p.dqb ? 1.f / (delayed_sx(p.dq[0]) * p.dqb[0]) : p.dq[0])
       : 1.f;
+  // STATS: per-lane column sums of the stored (bf16-rounded) values and
+  // their squares over this lane's 16 rows; lanes past Cout keep zeros
+  float cs[2] = {}, cq[2] = {};
   #pragma unroll
   for (int nf = 0; nf < 2; ++nf) {
     int n = n0 + wn0 + nf * 16 + fr;
@@ -1074,8 +1072,48 @@ __global__ __launch_bounds__(NTHREADS) void conv_fp8_kernel(ConvParams p) {
         int rl = wm0 + mf * 16 + fg * 4 + r;
         if (!sm.rowok[rl]) continue;
         float v = apply_act(acc[mf][nf][r] * dqs + bv, p.act, p.slope);
-        p.y[sm.rowyb[rl] + n] = f2b(v);
+        short hv = f2b(v);
+        p.y[sm.rowyb[rl] + n] = hv;
+        if (STATS) {
+          float fv = b2f(hv);
+          cs[nf] += fv;
+          cq[nf] += fv * fv;
+        }
       }
+    }
+  }
+
+  // InstanceNorm partial slabs, the epilogue of conv_glds_kernel on this
+  // kernel's fixed 2x2-wave 128x64 tile: the four lane>>4 row groups fold
+  // with two xor shuffles, the two wave rows meet in LDS, one thread per
+  // column adds them in wave-row order. No atomics, fixed order. The
+  // final K-loop barrier has retired every read of the staging buffers,
+  // so A[0] (16 KiB >= 2*BN*2 floats) is free to hold the partials.
+  if (STATS) {
+    float* red = reinterpret_cast<float*>(sm.A[0]);  // [2][BN][2]
+    static_assert(2 * BN * 2 * sizeof(float) <= sizeof(sm.A[0]), "red");
+    #pragma unroll
+    for (int nf = 0; nf < 2; ++nf) {
+      float s = cs[nf], q = cq[nf];
+      s += __shfl_xor(s, 16, 64);
+      q += __shfl_xor(q, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      q += __shfl_xor(q, 32, 64);
+      if (fg == 0) {
+        int col = wn0 + nf * 16 + fr;
+        red[(wr * BN + col) * 2] = s;
+        red[(wr * BN + col) * 2 + 1] = q;
+      }
+    }
+    __syncthreads();
+    if (tid < BN && n0 + tid < p.Cout) {
+      float s = red[tid * 2] + red[(BN + tid) * 2];
+      float q = red[tid * 2 + 1] + red[(BN + tid) * 2 + 1];
+      const int b = mt / p.tps;
+      const int slice = mt - b * p.tps;
+      const long o = ((long)slice * p.B + b) * p.Cout + n0 + tid;
+      p.psum[o] = s;
+      p.psq[o] = q;
     }
   }
 }
@@ -1938,13 +1976,18 @@ static bool phased_eligible(const ConvParams& p, bool is_convt) {
 // 128^2 (<= today's slice count) and a loss at 256^2 (512 slabs vs 128).
 // CYG_NO_CONV_STATS=1 turns the path off; CYG_CONV_STATS_MAXSLABS moves
 // the cap for A/B runs.
-static int stats_slabs(const ConvParams& p, bool is_convt, int* tps) {
+static int stats_cap() {
   static const int cap = []() {
     const char* off = getenv("CYG_NO_CONV_STATS");
     if (off && off[0] == '1') return 0;
     const char* e = getenv("CYG_CONV_STATS_MAXSLABS");
     return e ? atoi(e) : 128;
   }();
+  return cap;
+}
+
+static int stats_slabs(const ConvParams& p, bool is_convt, int* tps) {
+  const int cap = stats_cap();
   if (cap <= 0 || !glds_eligible(p) || p.Cout <= 16 || (p.Cout % 8) != 0)
     return 0;
   long per, ns;
@@ -2323,11 +2366,24 @@ void amax_roll(at::Tensor arena, int64_t n) {
                      (float*)arena.mutable_data_ptr(), (int)n, cap);
 }
 
-at::Tensor conv2d_fp8_fwd(at::Tensor xq, at::Tensor wq, at::Tensor dq,
-                          c10::optional<at::Tensor> sw,
-                          c10::optional<at::Tensor> bias, int64_t stride,
-                          int64_t pt, int64_t pb, int64_t pl, int64_t pr,
-                          bool reflect, int64_t act, double slope) {
+// conv_fp8_kernel always runs 128x64 tiles in plain row order, so the
+// stats_slabs rule reduces to: every M-tile inside one sample, the slab
+// count under the same cap, and the same Cout limits.
+static int stats_slabs_fp8(const ConvParams& p) {
+  const int cap = stats_cap();
+  if (cap <= 0 || p.Cout <= 16 || (p.Cout % 8) != 0) return 0;
+  long per = (long)p.OH * p.OW;
+  if (per % BM != 0 || per / BM > cap) return 0;
+  return (int)(per / BM);
+}
+
+// want_stats: {y, psum, psq} when stats_slabs_fp8 finds the call eligible,
+// {y} otherwise; y is the same either way.
+static std::vector<at::Tensor> conv2d_fp8_fwd_impl(
+    at::Tensor xq, at::Tensor wq, at::Tensor dq, c10::optional<at::Tensor> sw,
+    c10::optional<at::Tensor> bias, int64_t stride, int64_t pt, int64_t pb,
+    int64_t pl, int64_t pr, bool reflect, int64_t act, double slope,
+    bool want_stats) {
   TORCH_CHECK(xq.is_cuda() && xq.scalar_type() == at::kByte && xq.is_contiguous());
   TORCH_CHECK(wq.scalar_type() == at::kByte && wq.is_contiguous());
   TORCH_CHECK(xq.size(3) == wq.size(3) && xq.size(3) % 16 == 0,
@@ -2357,14 +2413,52 @@ at::Tensor conv2d_fp8_fwd(at::Tensor xq, at::Tensor wq, at::Tensor dq,
   p.ntiles = cdiv(p.Cout, BN);
   TORCH_CHECK((long)p.B * H * W * p.Cin < (1L << 31) &&
               (long)p.Cout * p.KTOT < (1L << 31));
+  std::vector<at::Tensor> out{y};
+  const int ns = want_stats ? stats_slabs_fp8(p) : 0;
+  if (ns > 0) {
+    auto ps = at::empty({2, ns, (long)p.B, (long)p.Cout},
+                        y.options().dtype(at::kFloat));
+    p.psum = (float*)ps.mutable_data_ptr();
+    p.psq = p.psum + (long)ns * p.B * p.Cout;
+    p.tps = ns;
+    out.push_back(ps[0]);
+    out.push_back(ps[1]);
+  }
   auto stream = at::cuda::getCurrentCUDAStream();
   dim3 grid(p.mtiles * p.ntiles);
+#define LAUNCH_FP8(S)                                                        \
+  do {                                                                       \
+    if (ns > 0)                                                              \
+      hipLaunchKernelGGL((conv_fp8_kernel<S, true>), grid, dim3(NTHREADS),   \
+                         0, stream, p);                                      \
+    else                                                                     \
+      hipLaunchKernelGGL((conv_fp8_kernel<S, false>), grid, dim3(NTHREADS),  \
+                         0, stream, p);                                      \
+  } while (0)
   switch (p.stride) {
-    case 1: hipLaunchKernelGGL((conv_fp8_kernel<1>), grid, dim3(NTHREADS), 0, stream, p); break;
-    case 2: hipLaunchKernelGGL((conv_fp8_kernel<2>), grid, dim3(NTHREADS), 0, stream, p); break;
-    default: hipLaunchKernelGGL((conv_fp8_kernel<0>), grid, dim3(NTHREADS), 0, stream, p);
+    case 1: LAUNCH_FP8(1); break;
+    case 2: LAUNCH_FP8(2); break;
+    default: LAUNCH_FP8(0);
   }
-  return y;
+#undef LAUNCH_FP8
+  return out;
+}
+
+at::Tensor conv2d_fp8_fwd(at::Tensor xq, at::Tensor wq, at::Tensor dq,
+                          c10::optional<at::Tensor> sw,
+                          c10::optional<at::Tensor> bias, int64_t stride,
+                          int64_t pt, int64_t pb, int64_t pl, int64_t pr,
+                          bool reflect, int64_t act, double slope) {
+  return conv2d_fp8_fwd_impl(xq, wq, dq, sw, bias, stride, pt, pb, pl, pr,
+                             reflect, act, slope, false)[0];
+}
+
+std::vector<at::Tensor> conv2d_fp8_fwd_stats(
+    at::Tensor xq, at::Tensor wq, at::Tensor dq, c10::optional<at::Tensor> sw,
+    c10::optional<at::Tensor> bias, int64_t stride, int64_t pt, int64_t pb,
+    int64_t pl, int64_t pr, bool reflect, int64_t act, double slope) {
+  return conv2d_fp8_fwd_impl(xq, wq, dq, sw, bias, stride, pt, pb, pl, pr,
+                             reflect, act, slope, true);
 }
 
 // ---- glds probe (test aid): verify raw_ptr_buffer_load_lds semantics ----

@@ -156,14 +156,24 @@ DEV float in_affine(float xv, float m, float rs, float g, float b) {
 // act (+ residual); slice-0 blocks also persist mean/rstd for backward.
 // S slices the grid; NS is the number of slabs to sum (== S after
 // in_reduce, HW/128 when the conv epilogue produced them) ----
+//
+// Q8 (compile-time, so the plain instantiation's row loop is untouched):
+// the kernel also hands the consuming fp8 conv its operand. Every 16 B of
+// bf16 it stores goes out a second time as 8 B of e4m3 in yq, quantised
+// from the bf16-ROUNDED value with delayed_sx(amax_prev[0]) — the bytes
+// quant_fp8_d would produce from y — and max|y| block-reduces into ONE
+// atomicMax per block on amax_cur (grid B*S <= ~512 blocks; see the
+// same-address-atomic note on quant_fp8_d_kernel).
 constexpr int MAXC = 2048;
+template <bool Q8>
 __global__ __launch_bounds__(NT) void in_norm_kernel(
     const short* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ psum,
     const float* __restrict__ psq, float* __restrict__ mean,
     float* __restrict__ rstd, const short* __restrict__ res,
     short* __restrict__ y, int B, long HW, int C, int S, int NS, int act,
-    float slope, float eps) {
+    float slope, float eps, unsigned char* __restrict__ yq,
+    const float* __restrict__ amax_prev, float* __restrict__ amax_cur) {
   int b = blockIdx.x / S;
   int sl = blockIdx.x % S;
   long rows = (HW + S - 1) / S;
@@ -260,6 +270,8 @@ __global__ __launch_bounds__(NT) void in_norm_kernel(
   }
   __syncthreads();
 
+  float qs = 0.f, mx = 0.f;
+  if constexpr (Q8) qs = delayed_sx(amax_prev[0]);
   {
     int g = tid % gpr;
     int rstep = NT / gpr;
@@ -271,14 +283,36 @@ __global__ __launch_bounds__(NT) void in_norm_kernel(
       v8s rv = {};
       if (res) rv = *(const v8s*)(res + off);
       v8s out;
+      alignas(8) unsigned char oq[8];
       #pragma unroll
       for (int j = 0; j < 8; ++j) {
         int c = g * 8 + j;
         float val = in_affine(b2f(v[j]), sm[c], sr[c], gamma[c], beta[c]);
         if (res) val += b2f(rv[j]);
         out[j] = f2b(apply_act(val, act, slope));
+        if constexpr (Q8) {
+          float fv = b2f(out[j]);
+          mx = fmaxf(mx, fabsf(fv));
+          oq[j] = f2e4m3(fv, qs);
+        }
       }
       *(v8s*)(y + off) = out;
+      if constexpr (Q8) *(uint2*)(yq + off) = *(uint2*)oq;
+    }
+  }
+  if constexpr (Q8) {
+    // block max: xor-shuffles inside each wave, then the NT/64 waves meet
+    // in LDS; max is exact in any order
+    __shared__ float wmax[NT / 64];
+    #pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if ((tid & 63) == 0) wmax[tid >> 6] = mx;
+    __syncthreads();
+    if (tid == 0) {
+      #pragma unroll
+      for (int k = 1; k < NT / 64; ++k) mx = fmaxf(mx, wmax[k]);
+      // nonneg float bits order == value order
+      atomicMax((unsigned*)amax_cur, __float_as_uint(mx));
     }
   }
 }
@@ -1063,13 +1097,13 @@ static int slices_for(long HW, int B) {
   return std::max(1, s);
 }
 
-std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
-                                     at::Tensor beta, double eps, int64_t act,
-                                     double slope,
-                                     c10::optional<at::Tensor> residual,
-                                     c10::optional<at::Tensor> psum_in,
-                                     c10::optional<at::Tensor> psq_in,
-                                     int64_t nslabs) {
+// amax_prev/amax_cur given (instnorm_fwd_q8): the normalize pass also
+// writes the consumer's e4m3 operand and returns {y, mean, rstd, yq}.
+static std::vector<at::Tensor> instnorm_fwd_impl(
+    at::Tensor x, at::Tensor gamma, at::Tensor beta, double eps, int64_t act,
+    double slope, c10::optional<at::Tensor> residual,
+    c10::optional<at::Tensor> psum_in, c10::optional<at::Tensor> psq_in,
+    int64_t nslabs, const at::Tensor* amax_prev, at::Tensor* amax_cur) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous());
   int B = x.size(0), C = x.size(3);
   long HW = (long)x.size(1) * x.size(2);
@@ -1083,6 +1117,49 @@ std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
   auto y = at::empty_like(x);
   const short* resf = residual.has_value()
                           ? (const short*)residual->const_data_ptr() : nullptr;
+  const bool q8 = amax_prev != nullptr;
+  at::Tensor yq;
+  if (q8) {
+    TORCH_CHECK(amax_cur != nullptr && amax_prev->is_cuda() &&
+                amax_cur->is_cuda() &&
+                amax_prev->scalar_type() == at::kFloat &&
+                amax_cur->scalar_type() == at::kFloat &&
+                amax_prev->numel() >= 1 && amax_cur->numel() >= 1,
+                "instnorm_fwd_q8: bad amax slots");
+    yq = at::empty_like(x, x.options().dtype(at::kByte));
+  }
+  // the normalize launch shared by every route below; ps == nullptr reads
+  // the stats in_stats_kernel left in mean/rstd
+  auto launch_norm = [&](const float* ps, const float* pq, int ns) {
+    if (q8)
+      hipLaunchKernelGGL(in_norm_kernel<true>, dim3(B * S), dim3(NT), 0,
+                         stream, (const short*)x.const_data_ptr(),
+                         (const float*)gamma.const_data_ptr(),
+                         (const float*)beta.const_data_ptr(), ps, pq,
+                         (float*)mean.mutable_data_ptr(),
+                         (float*)rstd.mutable_data_ptr(), resf,
+                         (short*)y.mutable_data_ptr(), B, HW, C, S, ns,
+                         (int)act, (float)slope, (float)eps,
+                         (unsigned char*)yq.mutable_data_ptr(),
+                         (const float*)amax_prev->const_data_ptr(),
+                         (float*)amax_cur->mutable_data_ptr());
+    else
+      hipLaunchKernelGGL(in_norm_kernel<false>, dim3(B * S), dim3(NT), 0,
+                         stream, (const short*)x.const_data_ptr(),
+                         (const float*)gamma.const_data_ptr(),
+                         (const float*)beta.const_data_ptr(), ps, pq,
+                         (float*)mean.mutable_data_ptr(),
+                         (float*)rstd.mutable_data_ptr(), resf,
+                         (short*)y.mutable_data_ptr(), B, HW, C, S, ns,
+                         (int)act, (float)slope, (float)eps,
+                         (unsigned char*)nullptr, (const float*)nullptr,
+                         (float*)nullptr);
+  };
+  auto result = [&]() {
+    std::vector<at::Tensor> out{y, mean, rstd};
+    if (q8) out.push_back(yq);
+    return out;
+  };
 
   if (psum_in.has_value()) {
     // slabs precomputed by the producing conv's epilogue ([nslabs,B,C]
@@ -1095,17 +1172,9 @@ std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
                 psum_in->numel() == nslabs * B * C &&
                 psq_in->numel() == nslabs * B * C,
                 "instnorm_fwd: bad precomputed slabs");
-    hipLaunchKernelGGL(in_norm_kernel, dim3(B * S), dim3(NT), 0, stream,
-                       (const short*)x.const_data_ptr(),
-                       (const float*)gamma.const_data_ptr(),
-                       (const float*)beta.const_data_ptr(),
-                       (const float*)psum_in->const_data_ptr(),
-                       (const float*)psq_in->const_data_ptr(),
-                       (float*)mean.mutable_data_ptr(),
-                       (float*)rstd.mutable_data_ptr(), resf,
-                       (short*)y.mutable_data_ptr(), B, HW, C, S,
-                       (int)nslabs, (int)act, (float)slope, (float)eps);
-    return {y, mean, rstd};
+    launch_norm((const float*)psum_in->const_data_ptr(),
+                (const float*)psq_in->const_data_ptr(), (int)nslabs);
+    return result();
   }
 
   static int fused_cap = []() {
@@ -1123,7 +1192,9 @@ std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
       return 0;
     return bpc * ncu;
   }();
-  if (fused_cap > 0 && B < fused_cap) {
+  // the single-launch kernel has no Q8 form: a twin request takes the
+  // two-kernel route
+  if (!q8 && fused_cap > 0 && B < fused_cap) {
     int Sf = std::max(1, std::min(S, fused_cap / B));
     auto gq = at::empty({(long)Sf * B * C}, x.options().dtype(at::kLong));
     auto arr = at::empty({B}, x.options().dtype(at::kInt));
@@ -1148,8 +1219,6 @@ std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
                      (const short*)x.const_data_ptr(),
                      (float*)psum.mutable_data_ptr(),
                      (float*)psq.mutable_data_ptr(), B, HW, C, S);
-  const short* res = residual.has_value()
-                         ? (const short*)residual->const_data_ptr() : nullptr;
   static bool use_stats = []() {
     // measured NEGATIVE (318 vs 324 img/s): the near-serial B-block
     // stats kernel delays the normalize more than the redundant (L2-hot)
@@ -1166,27 +1235,38 @@ std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
                        (float*)mean.mutable_data_ptr(),
                        (float*)rstd.mutable_data_ptr(), B, HW, C, S,
                        (float)eps);
-    hipLaunchKernelGGL(in_norm_kernel, dim3(B * S), dim3(NT), 0, stream,
-                       (const short*)x.const_data_ptr(),
-                       (const float*)gamma.const_data_ptr(),
-                       (const float*)beta.const_data_ptr(), nullptr, nullptr,
-                       (float*)mean.mutable_data_ptr(),
-                       (float*)rstd.mutable_data_ptr(), res,
-                       (short*)y.mutable_data_ptr(), B, HW, C, S, S,
-                       (int)act, (float)slope, (float)eps);
-    return {y, mean, rstd};
+    launch_norm(nullptr, nullptr, S);
+    return result();
   }
-  hipLaunchKernelGGL(in_norm_kernel, dim3(B * S), dim3(NT), 0, stream,
-                     (const short*)x.const_data_ptr(),
-                     (const float*)gamma.const_data_ptr(),
-                     (const float*)beta.const_data_ptr(),
-                     (const float*)psum.const_data_ptr(),
-                     (const float*)psq.const_data_ptr(),
-                     (float*)mean.mutable_data_ptr(),
-                     (float*)rstd.mutable_data_ptr(), res,
-                     (short*)y.mutable_data_ptr(), B, HW, C, S, S,
-                     (int)act, (float)slope, (float)eps);
-  return {y, mean, rstd};
+  launch_norm((const float*)psum.const_data_ptr(),
+              (const float*)psq.const_data_ptr(), S);
+  return result();
+}
+
+std::vector<at::Tensor> instnorm_fwd(at::Tensor x, at::Tensor gamma,
+                                     at::Tensor beta, double eps, int64_t act,
+                                     double slope,
+                                     c10::optional<at::Tensor> residual,
+                                     c10::optional<at::Tensor> psum_in,
+                                     c10::optional<at::Tensor> psq_in,
+                                     int64_t nslabs) {
+  return instnorm_fwd_impl(x, gamma, beta, eps, act, slope, residual, psum_in,
+                           psq_in, nslabs, nullptr, nullptr);
+}
+
+// instnorm_fwd that also emits the e4m3 twin of y for the fp8 conv that
+// consumes it: yq == quant_fp8_d(y, amax_prev, .) byte for byte, and
+// amax_cur = max(amax_cur, max|y|). Returns {y, mean, rstd, yq}.
+std::vector<at::Tensor> instnorm_fwd_q8(at::Tensor x, at::Tensor gamma,
+                                        at::Tensor beta, double eps,
+                                        int64_t act, double slope,
+                                        c10::optional<at::Tensor> residual,
+                                        c10::optional<at::Tensor> psum_in,
+                                        c10::optional<at::Tensor> psq_in,
+                                        int64_t nslabs, at::Tensor amax_prev,
+                                        at::Tensor amax_cur) {
+  return instnorm_fwd_impl(x, gamma, beta, eps, act, slope, residual, psum_in,
+                           psq_in, nslabs, &amax_prev, &amax_cur);
 }
 
 // launch a backward kernel template with the mask mode chosen at run time

@@ -27,7 +27,8 @@ accumulation) and flow straight into the fp32 master's grad bucket.
 
 from __future__ import annotations
 
-from typing import Optional, Tuple
+import os
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -284,14 +285,86 @@ def fp8_mode() -> bool:
     return _FP8_MODE
 
 
+# Attribute under which an InstanceNorm output carries the e4m3 twin the
+# norm kernel wrote for the fp8 conv that consumes it: (yq, prev), yq uint8
+# of the tensor's own NHWC shape, prev the amax_prev slot view (of
+# ops.fp8_state) it was quantised with. Non-differentiable. The conv uses
+# it instead of running quant_fp8_d, but only when prev is its own
+# weight's slot (_twin_for).
+FP8_TWIN_ATTR = "_cyg_fp8_twin"
+
+
+class Fp8Consumer(NamedTuple):
+    """Hint for ops.norm.instance_norm: the conv that reads its output."""
+    weight: torch.Tensor   # the consumer's fp32 master weight (OHWI)
+    stride: int = 1
+
+
+def _knob_off(name: str) -> bool:
+    """CYG_NO_FP8_TWIN / CYG_NO_FP8_STATS, read per call."""
+    return os.environ.get(name) == "1"
+
+
+def takes_fp8_path(x: torch.Tensor, w: torch.Tensor, stride: int,
+                   pads=None, reflect: bool = False) -> bool:
+    """Would conv2d(x, w, stride=...) run the fp8 kernel while fp8 mode is
+    on? The ONE dispatch predicate: conv2d routes by it, and the producing
+    norm decides by it whether to emit an fp8 twin for that conv.
+
+    fp8 only where the 16x16x128 fp8 kernel + quant beats the bf16 glds
+    kernel (tools/fp8_micro.py on MI355X): the wide-channel stride-1 3x3
+    family at batch >= 12 (K3: 999 vs 715 TF/s) and the 4x4 s1 wide
+    discriminator conv. Elsewhere the per-tensor quantization overhead
+    cancels the MFMA-rate gain. The packed head comes first: skinny-Cout
+    convs gain more from dense-N bf16 packing than from fp8's rate. It is
+    7x7 only, so without pads (the norm's hint has none) the kernel-size
+    test below already excludes it."""
+    if x.dim() != 4 or w.dim() != 4 or x.dtype != torch.bfloat16:
+        return False
+    if pads is not None and _head_packable(x, w, stride, tuple(pads), reflect):
+        return False
+    return (w.shape[3] == x.shape[3]
+            and w.shape[3] % 16 == 0 and w.shape[3] >= 256
+            and stride == 1
+            and ((w.shape[1] == 3 and x.shape[0] >= 12)
+                 or w.shape[1] == 4))
+
+
+def _twin_for(x: torch.Tensor, w: torch.Tensor):
+    """The fp8 twin attached to x if it is this conv's operand: same shape
+    and device as x, and quantised with THIS weight's amax_prev slot (the
+    slot object itself, not just any slot). None -> quantise as usual."""
+    if _knob_off("CYG_NO_FP8_TWIN"):
+        return None
+    tw = getattr(x, FP8_TWIN_ATTR, None)
+    if tw is None:
+        return None
+    from . import fp8_state
+    xq, tw_prev = tw
+    ent = fp8_state.peek(w)
+    if (ent is None or tw_prev is not ent[0] or xq.shape != x.shape
+            or xq.device != x.device or xq.dtype != torch.uint8
+            or x.shape[3] < 8 or not x.is_contiguous()
+            or not xq.is_contiguous()):
+        return None
+    return xq
+
+
 class _ConvFp8Fn(torch.autograd.Function):
     """fp8 e4m3 forward conv with delayed per-tensor activation scaling
     (ops.fp8_state): quantization uses last step's amax — no separate
     amax reduction in the hot path — and the dequant factor is computed
-    inside the conv epilogue from the amax/sw scalars."""
+    inside the conv epilogue from the amax/sw scalars.
+
+    ``twin`` (non-differentiable) is x already quantised with this layer's
+    amax_prev by the kernel that produced x (see FP8_TWIN_ATTR); that
+    kernel also maxed this step's amax into amax_cur, so quant_fp8_d is
+    skipped. Bias-free, activation-free calls also return the
+    InstanceNorm slabs of y when the shape is eligible, like _ConvFn."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, stride, pads, reflect, act, slope):
+    def forward(ctx, x, w, bias, stride, pads, reflect, act, slope,
+                twin=None):
         from . import fp8_state
         ext = backend.ext()
         cout = w.shape[0]
@@ -300,18 +373,34 @@ class _ConvFp8Fn(torch.autograd.Function):
         prev, cur, fresh = fp8_state.slots_for(w)
         if fresh:  # bootstrap (eager, once per layer, pre-capture)
             prev.copy_(xp.detach().abs().amax().float().clamp(min=1e-12))
-        xq = ext.quant_fp8_d(xp, prev, cur)
+            twin = None  # cannot have been made with this (new) slot
+        xq = twin if twin is not None else ext.quant_fp8_d(xp, prev, cur)
         bc = compute_bias_p(bias, x) if bias is not None else None
-        y = ext.conv2d_fp8_fwd(xq, wq, prev, sw, bc, stride, *pads,
-                               reflect, act, slope)
+        slabs = ()
+        if (_want_stats(bias, act) and cout >= 8
+                and not _knob_off("CYG_NO_FP8_STATS")):
+            y, *slabs = ext.conv2d_fp8_fwd_stats(xq, wq, prev, sw, bc, stride,
+                                                 *pads, reflect, act, slope)
+        else:
+            y = ext.conv2d_fp8_fwd(xq, wq, prev, sw, bc, stride, *pads,
+                                   reflect, act, slope)
         if cout < 8:
             y = y[..., :cout].contiguous()
         ctx.save_for_backward(xp, w, y)
         ctx.conf = (stride, pads, reflect, act, slope, bias is not None,
                     x.shape[3])
+        if slabs:
+            # no zero-filled grads for the slab outputs in backward
+            ctx.set_materialize_grads(False)
+            ctx.mark_non_differentiable(*slabs)
+            return (y, *slabs)
         return y
 
-    backward = _ConvFn.backward
+    @staticmethod
+    def backward(ctx, dy, *_):
+        # bf16 backward of _ConvFn on the saved bf16 activations; the twin
+        # input has no gradient
+        return _ConvFn.backward(ctx, dy) + (None,)
 
 
 class _ConvTFn(torch.autograd.Function):
@@ -389,18 +478,10 @@ def conv2d(
         # bf16 packing than from fp8's rate (and skip fp8's quant cost)
         if _head_packable(x, w, stride, pads, pad_mode == "reflect"):
             return _ConvHeadPackedFn.apply(x, w, bias, a, slope)
-        # fp8 only where the 16x16x128 fp8 kernel + quant beats the bf16
-        # glds kernel (tools/fp8_micro.py on MI355X): the wide-channel
-        # stride-1 3x3 family at batch >= 12 (K3: 999 vs 715 TF/s) and
-        # the 4x4 s1 wide discriminator conv. Elsewhere the per-tensor
-        # quantization overhead cancels the MFMA-rate gain.
-        if (_FP8_MODE and x.dtype == torch.bfloat16
-                and w.shape[3] % 16 == 0 and w.shape[3] >= 256
-                and stride == 1
-                and ((w.shape[1] == 3 and x.shape[0] >= 12)
-                     or w.shape[1] == 4)):
-            return _ConvFp8Fn.apply(x, w, bias, stride, pads,
-                                    pad_mode == "reflect", a, slope)
+        if _FP8_MODE and takes_fp8_path(x, w, stride):
+            return _attach_slabs(_ConvFp8Fn.apply(
+                x, w, bias, stride, pads, pad_mode == "reflect", a, slope,
+                _twin_for(x, w)))
         return _attach_slabs(_ConvFn.apply(x, w, bias, stride, pads,
                                            pad_mode == "reflect", a, slope))
     wc = w if w.dtype == x.dtype else w.to(x.dtype)

@@ -38,6 +38,17 @@ def slots_for(w: torch.Tensor):
     return ent[0], ent[1], fresh
 
 
+def peek(w: torch.Tensor):
+    """(amax_prev view, amax_cur view) if the layer keyed by w already owns
+    a slot, else None. Read-only: allocates nothing and leaves the
+    ``fresh`` report of the layer's first slots_for call alone, so a
+    producer that looks ahead never takes the consumer's bootstrap."""
+    ent = _slots.get(w)
+    if ent is None or _arena is None or _arena.device != w.device:
+        return None
+    return ent
+
+
 def roll():
     """prev <- cur, cur <- 0 for every registered layer (call once per
     optimizer step while fp8 mode is on)."""

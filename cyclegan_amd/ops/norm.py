@@ -20,7 +20,9 @@ from typing import Optional
 import torch
 
 from . import backend
-from .conv import ACT_NONE, ACT_RELU, ACT_LRELU, IN_SLABS_ATTR, _ACT
+from . import conv as _conv
+from .conv import (ACT_NONE, ACT_RELU, ACT_LRELU, FP8_TWIN_ATTR,
+                   IN_SLABS_ATTR, _ACT, Fp8Consumer)
 
 EPS_DEFAULT = 1e-3  # tfa InstanceNormalization default
 
@@ -54,11 +56,21 @@ def _mask_from_x(act: int) -> bool:
 
 
 class _InstNormFn(torch.autograd.Function):
+    """amax_prev/amax_cur (the consumer conv's fp8_state slots, or None):
+    the normalize kernel also writes the e4m3 twin of y and the call
+    returns (y, yq), yq non-differentiable."""
+
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, act, slope, residual, psum, psq):
+    def forward(ctx, x, gamma, beta, eps, act, slope, residual, psum, psq,
+                amax_prev=None, amax_cur=None):
         ext = backend.ext()
         betaf = beta.float()
-        if psum is not None:
+        yq = None
+        if amax_prev is not None:
+            y, mean, rstd, yq = ext.instnorm_fwd_q8(
+                x, gamma.float(), betaf, eps, act, slope, residual, psum, psq,
+                psum.shape[0] if psum is not None else 0, amax_prev, amax_cur)
+        elif psum is not None:
             y, mean, rstd = ext.instnorm_fwd(x, gamma.float(), betaf, eps, act,
                                              slope, residual, psum, psq,
                                              psum.shape[0])
@@ -67,10 +79,17 @@ class _InstNormFn(torch.autograd.Function):
                                              slope, residual)
         ctx.save_for_backward(x, gamma, mean, rstd, y, betaf)
         ctx.conf = (eps, act, slope, residual is not None)
+        if yq is not None:
+            # no zero-filled grad for the twin in backward
+            ctx.set_materialize_grads(False)
+            ctx.mark_non_differentiable(yq)
+            return y, yq
         return y
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, *_):
+        if dy is None:  # only with set_materialize_grads(False): y unused
+            return (None,) * 11
         x, gamma, mean, rstd, y, betaf = ctx.saved_tensors
         eps, act, slope, has_res = ctx.conf
         ext = backend.ext()
@@ -87,7 +106,7 @@ class _InstNormFn(torch.autograd.Function):
             dx, dgamma, dbeta = ext.instnorm_bwd(
                 dy, x, gamma.float(), mean, rstd, yact, act, slope, betaf)
         return (dx, dgamma.to(gamma.dtype), dbeta, None, None, None, dres,
-                None, None)
+                None, None, None, None)
 
 
 def _slabs_for(x: torch.Tensor):
@@ -103,6 +122,21 @@ def _slabs_for(x: torch.Tensor):
     return psum, psq
 
 
+def _twin_slots(x: torch.Tensor, consumer: Optional[Fp8Consumer]):
+    """(amax_prev, amax_cur) of the fp8 conv that will read this norm's
+    output, when a twin is worth making: fp8 mode on, conv2d's own
+    dispatch predicate says that conv takes the fp8 path for a tensor of
+    x's shape and dtype (the norm keeps both), and the layer already owns
+    a slot. On a layer's first eager call there is none: no twin, and the
+    conv bootstraps its scale as before. CYG_NO_FP8_TWIN=1 turns it off."""
+    if (consumer is None or not _conv.fp8_mode()
+            or os.environ.get("CYG_NO_FP8_TWIN") == "1"
+            or not _conv.takes_fp8_path(x, consumer.weight, consumer.stride)):
+        return None
+    from . import fp8_state
+    return fp8_state.peek(consumer.weight)
+
+
 def instance_norm(
     x: torch.Tensor,
     gamma: torch.Tensor,
@@ -111,10 +145,20 @@ def instance_norm(
     act: Optional[str] = None,
     slope: float = 0.2,
     residual: Optional[torch.Tensor] = None,
+    fp8_consumer: Optional[Fp8Consumer] = None,
 ) -> torch.Tensor:
+    """``fp8_consumer`` names the conv that reads the result. In fp8 mode
+    on the HIP path the result then carries that conv's e4m3 operand
+    (FP8_TWIN_ATTR); everywhere else the hint is ignored."""
     a = _ACT[act]
     if backend.use_hip(x, gamma):
         psum, psq = _slabs_for(x)
+        slots = _twin_slots(x, fp8_consumer)
+        if slots is not None:
+            y, yq = _InstNormFn.apply(x, gamma, beta, eps, a, slope, residual,
+                                      psum, psq, slots[0], slots[1])
+            setattr(y, FP8_TWIN_ATTR, (yq, slots[0]))
+            return y
         return _InstNormFn.apply(x, gamma, beta, eps, a, slope, residual,
                                  psum, psq)
     return _in_ref(x, gamma, beta, eps, a, slope, residual)
