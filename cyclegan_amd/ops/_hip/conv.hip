@@ -1,11 +1,25 @@
 // Implicit-GEMM NHWC convolutions on gfx950 MFMA (bf16 in, fp32 accumulate).
 //
-// Three kernels cover every conv op in the framework:
-//   conv_fwd_kernel   y[b,oh,ow,n] = act(Σ_{dk,ci} x[b,oh*s+dk-pt,ci]·w[n,dk,ci] + bias)
-//                     (also conv_transpose dgrad, via the channel-transposed weight)
-//   convt_fwd_kernel  y[b,i,j,n]   = act(Σ_{dk,ci; i=s*o+dk-pt} in[b,o,ci]·w[n,dk,ci] + bias)
-//                     (also conv2d dgrad: same gather, channel-transposed weight, no tap flip)
-//   wgrad_kernel      dw[n,dk,ci] += Σ_{b,o} x_patch[m,(dk,ci)]·dy[m,n]   (fp32, split-M atomics)
+// Two gathers and one weight gradient cover every conv op in the framework
+// (SURVEY §2.3 K1-K6):
+//   conv   (IS_CONVT=false)  y[b,oh,ow,n] = act(Σ_{dk,ci} x[b,oh*s+dk-pt,ci]·w[n,dk,ci] + bias)
+//          (also conv_transpose dgrad, via the channel-transposed weight)
+//   convT  (IS_CONVT=true)   y[b,i,j,n]   = act(Σ_{dk,ci; i=s*o+dk-pt} in[b,o,ci]·w[n,dk,ci] + bias)
+//          (also conv2d dgrad: same gather, channel-transposed weight, no tap flip)
+//   wgrad  dw[n,dk,ci] = Σ_{b,o} x_patch[m,(dk,ci)]·dy[m,n]   (fp32, split-M)
+//
+// Kernels in this file:
+//   conv_glds_kernel     production conv/convT: LDS-DMA staging, n-tile
+//                        16/64/128 (conv_ntile), PHASED form for the
+//                        stride-2 convT; optional InstanceNorm slab epilogue
+//   conv_gemm_kernel     fallback for Cin % 8 != 0 or tensors past 2 GiB
+//   conv_fp8_kernel      e4m3 forward conv (quant_fp8_kernel,
+//                        quant_fp8_d_kernel, amax_roll_kernel feed it)
+//   wgrad_glds_kernel    production wgrad: split-M slabs summed by
+//                        wgrad_reduce_kernel, no atomics
+//   wgrad_kernel         fallback for Cin % 8 != 0 or Cout % 8 != 0
+//                        (fp32 atomics over the split-M slices)
+//   reflect_fold_kernel  folds the padded-frame dgrad back over the mirrors
 //
 // GEMM view: M = B*OH*OW output pixels, N = Cout, K = KH*KW*Cin, with the
 // im2col A-tile gathered on the fly (reflection padding = a load-index
@@ -20,9 +34,7 @@
 // im2col addressing, XCD-chunked blockIdx->tile mapping;
 // mfma_f32_16x16x32_bf16 fragments: A row = lane&15, k = (lane>>4)*8..+8;
 // D col = lane&15, row = (lane>>4)*4 + reg (verified by tests/test_ops_gpu.py
-// via the mfma_probe binding and oracle comparisons). A halo-tiled direct
-// head-conv kernel exists behind CYG_HALO=1 (see NOTES.md). The plain
-// conv_gemm_kernel remains as the unaligned-channel fallback.
+// via the mfma_probe binding of probes.hip and oracle comparisons).
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -257,7 +269,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_gemm_kernel(ConvParams p) {
 // the buffer descriptor turns into zeros. One __shared__ object only
 // (hipcc de-pipelines glds next to a second one).
 
-template <int NBUF, int BNT = BN>
+template <int BNT>
 struct ConvSmemT {
   // small arrays first: keeps their ds offsets within the 16-bit
   // immediate range even when the tile images exceed 64 KiB
@@ -266,13 +278,13 @@ struct ConvSmemT {
   unsigned rowxb[BM];  // byte offset of batch base (tensors < 4 GiB)
   char rowok[BM];
   char _pad[16 - (BM % 16 ? BM % 16 : 16)];
-  short A[NBUF][BM * BK];
-  short Bt[NBUF][BNT * BK];
+  short A[2][BM * BK];   // double-buffered
+  short Bt[2][BNT * BK];
 };
-using ConvSmem = ConvSmemT<2>;
 
-template <bool IS_CONVT, int STRIDE, int NBUF = 2, int NW = 4, int BNT = BN,
-          bool PHASED = false>
+constexpr int NW = 8;  // waves per block of the glds kernels (conv, wgrad)
+
+template <bool IS_CONVT, int STRIDE, int BNT, bool PHASED = false>
 __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
   constexpr int NT = NW * 64;        // threads
   constexpr int API = 16 / NW;       // A glds instructions per wave
@@ -286,7 +298,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
   // dynamic LDS (the BNT=128 image exceeds the 64 KiB static limit);
   // ONE region, 16-B aligned (G17), opted-in at launch time.
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  auto& sm = *reinterpret_cast<ConvSmemT<NBUF, BNT>*>(smem_raw);
+  auto& sm = *reinterpret_cast<ConvSmemT<BNT>*>(smem_raw);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -506,17 +518,6 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
   init_state();
   stage(0);
   __syncthreads();
-#ifdef CYG_DEBUG_EPI
-  if (bid == 0 && tid == 0)
-    printf("dbg NW=%d BNT=%d API=%d TBI=%d BPI=%d NF=%d NWC=%d MF=%d nk=%d "
-           "kv=%d klog=%d bvo0=%u bnv0=%d avo0=%u avalid0=%d "
-           "A0123=%d %d %d %d Bt0123=%d %d %d %d\n",
-           NW, BNT, API, TBI, BPI, NF, NWC, MF, nk, (int)kv, klog, bvo[0],
-           (int)bnv[0], avo[0], (int)avalid[0],
-           (int)sm.A[0][0], (int)sm.A[0][1], (int)sm.A[0][2], (int)sm.A[0][3],
-           (int)sm.Bt[0][0], (int)sm.Bt[0][1], (int)sm.Bt[0][2],
-           (int)sm.Bt[0][3]);
-#endif
 
   for (int kt = 0; kt < nk; ++kt) {
     if (kt + 1 < nk) {
@@ -559,13 +560,6 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
       for (int r = 0; r < 4; ++r) {
         int rl = wm0 + mf * 16 + fg * 4 + r;
         if (!sm.rowok[rl]) continue;
-#ifdef CYG_DEBUG_EPI
-        if (sm.rowyb[rl] < 0 || sm.rowyb[rl] + n >= p.M * p.Cout) {
-          printf("EPI OOB bid=%d tid=%d rl=%d rowyb=%ld n=%d\n",
-                 bid, tid, rl, (long)sm.rowyb[rl], n);
-          continue;
-        }
-#endif
         float v = apply_act(acc[mf][nf][r] + bv, p.act, p.slope);
         short hv = f2b(v);
         p.y[sm.rowyb[rl] + n] = hv;
@@ -612,154 +606,6 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
       const long o = ((long)slice * p.B + b) * p.Cout + n0 + tid;
       p.psum[o] = s;
       p.psq[o] = q;
-    }
-  }
-}
-
-// ---------------- halo-tiled direct conv (tiny-Cout heads) ----------------
-// The generator head 7x7 (64->3, padded to 8) is gather-bound in the
-// implicit-GEMM path: every input byte crosses the load path KH*KW times
-// (1.6 GB through L2 for 34 MB of unique input). This kernel stages the
-// whole input halo of an output-row tile in LDS ONCE and slides the
-// filter window inside LDS, so HBM traffic drops to the unique bytes.
-//
-// One block = HB_BM consecutive output pixels of one output row.
-// LDS: x halo [KH][HB_BM+KW-1][Cin] bf16, XOR ch-group swizzle riding the
-//      glds SOURCE address (same trick as the GEMM tiles, guide rule 21);
-//      w [nk][4 kgrp][8 n][8 bf16] staged by plain loads (n >= 8 MFMA
-//      fragments read zero — Cout is exactly 8 after channel padding).
-// Gate (host): stride 1, !convT, Cout == 8, Cin % 32 == 0, LDS fits.
-constexpr int HB_BM = 64;
-
-template <int NW = 4>
-__global__ __launch_bounds__(NW * 64) void conv_halo_kernel(ConvParams p) {
-  constexpr int NT = NW * 64;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = tid >> 6;
-  const int tiles_w = (p.OW + HB_BM - 1) / HB_BM;
-  const int bid = xcd_chunk(blockIdx.x, gridDim.x);
-  const int owt = bid % tiles_w;
-  const int t2 = bid / tiles_w;
-  const int oh = t2 % p.OH;
-  const int b = t2 / p.OH;
-  const int ow0 = owt * HB_BM;
-  const int CW = HB_BM + p.KW - 1;
-  constexpr int CG = 8;                 // Cin = 64 specialist (head convs)
-  constexpr int SL = CG + 1;            // 9 slots/pixel: the pad slot makes
-                                        // the pixel stride 36 words, which
-                                        // spreads the 16 fragment lanes
-                                        // over all 64 LDS banks (no XOR,
-                                        // conflict-free ds_read_b128)
-  constexpr int halves = 2;             // 32-elem K-steps per tap
-  const int nk = p.KH * p.KW * halves;
-
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  short* xs = (short*)smem_raw;                       // halo image
-  const int xgr = p.KH * CW * SL;                     // halo granules
-  const int xgr_pad = ((xgr + NT - 1) / NT) * NT;
-
-  auto rx = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)p.x, 0, (unsigned)((long)p.B * p.H * p.W * p.Cin * 2),
-      0x00020000);
-
-  // ---- stage halo: glds, swizzle on the source ch-group ----
-  // (row, col, chs) advance incrementally across rounds: NT granules =
-  // NT/CG columns per step, so the loop runs without integer divisions
-  // (runtime-divisor idiv is ~40 VALU cycles and this is a latency-
-  // critical serial section at 1-2 blocks/CU).
-  const long xbase = (long)b * p.H * p.W * p.Cin;
-  {
-    int g = w * 64 + lane;
-    int chs = g % SL;                     // constexpr divisor: cheap
-    int pix = g / SL;
-    int col = pix % CW;                   // once; then incremental
-    int row = pix / CW;
-    constexpr int dpix = NT / SL;         // pixels advanced per round
-    constexpr int dchs = NT - dpix * SL;  // slot advance per round
-    for (int g0 = 0; g0 < xgr_pad; g0 += NT) {
-      unsigned vo = 0xFF000000u;          // OOB (and pad slot) -> zeros
-      if (row < p.KH && chs < CG) {
-        int ih = oh - p.pt + row;
-        int iw = ow0 - p.pl + col;
-        bool okp = true;
-        if (p.reflect) {
-          ih = mirror_idx(ih, p.H);
-          iw = mirror_idx(iw, p.W);
-        } else {
-          okp = ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
-        }
-        if (okp)
-          vo = (unsigned)((xbase + ((long)ih * p.W + iw) * p.Cin + chs * 8) * 2);
-      }
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rx, (__attribute__((address_space(3))) void*)(xs + (long)(g0 + w * 64) * 8),
-          16, vo, 0, 0, 0);
-      chs += dchs;
-      col += dpix;
-      if (chs >= SL) { chs -= SL; ++col; }
-      while (col >= CW) { col -= CW; ++row; }
-    }
-  }
-
-  __syncthreads();  // drains the halo glds (vmcnt(0))
-
-  // ---- K loop: slide the window inside LDS ----
-  // NW=8: waves pair up on each m-fragment and split the K range in half
-  // (k-split), halving the per-wave latency chain; partials meet in LDS.
-  constexpr int KSPLIT = NW >= 8 ? 2 : 1;
-  const int mf = KSPLIT > 1 ? (w & 3) : w;
-  const int kh2 = KSPLIT > 1 ? (w >> 2) : 0;
-  const int fr = lane & 15;
-  const int fg = lane >> 4;
-  const int p0 = mf * 16;                 // wave's pixel base
-  const v8bf bz = {};
-  v4f acc = {};
-  const int k0 = kh2 * (nk / KSPLIT);
-  const int k1 = (kh2 == KSPLIT - 1) ? nk : (kh2 + 1) * (nk / KSPLIT);
-  int tap = k0 / halves, h = k0 - tap * halves;
-  int ty = tap / p.KW, tx = tap - ty * p.KW;
-  #pragma unroll 8
-  for (int kt = k0; kt < k1; ++kt) {
-    int col = p0 + fr + tx;
-    int chs = h * 4 + fg;
-    v8bf a = *(const v8bf*)(xs + (((ty * CW + col) * SL + chs) << 3));
-    // B straight from L2: the padded weight is 50 KB and shared by every
-    // block; k = kt*32 + fg*8, contiguous per lane, pipelined by the
-    // unroll. Keeping it OUT of LDS halves the block footprint -> 2
-    // blocks/CU, which is what lets the next block's halo fill overlap
-    // this block's MFMA tail.
-    v8bf bf = bz;
-    if (fr < 8)
-      bf = *(const v8bf*)(p.w + (long)fr * p.KTOT + kt * 32 + fg * 8);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bf, acc, 0, 0, 0);
-    if (++h == halves) {                  // advance (tap, half) counters
-      h = 0;
-      ++tap;
-      if (++tx == p.KW) { tx = 0; ++ty; }
-    }
-  }
-
-  if (KSPLIT > 1) {
-    // meet the k-split partials in the (no longer needed) halo LDS
-    __syncthreads();
-    float* red = (float*)xs;
-    if (kh2 == 1)
-      *(v4f*)&red[(mf * 64 + lane) * 4] = acc;
-    __syncthreads();
-    if (kh2 != 0) return;
-    acc += *(const v4f*)&red[(mf * 64 + lane) * 4];
-  }
-
-  // ---- epilogue: lane holds col n = fr, rows p0 + fg*4 + r ----
-  if (fr < p.Cout) {
-    float bv = p.bias ? b2f(p.bias[fr]) : 0.f;
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int ow = ow0 + p0 + fg * 4 + r;
-      if (ow >= p.OW) continue;
-      float v = apply_act(acc[r] + bv, p.act, p.slope);
-      p.y[(((long)b * p.OH + oh) * p.OW + ow) * p.Cout + fr] = f2b(v);
     }
   }
 }
@@ -1429,40 +1275,32 @@ DEV v4bfx tr16_read(const char* plds) {
       (__attribute__((address_space(3))) v4bfx*)plds);
 }
 
-template <int WBN, int KT = 1>
+template <int WBN>
 struct WgSmemT {
-  short A[2][KT * WG_BM * WG_BK];   // [ktile][m][k] swizzled
+  short A[2][WG_BM * WG_BK];        // [m][k] swizzled
   short D[2][WG_BM * WBN];          // [m][n] swizzled
 };
 
-// KT = k-tiles per block (2 for the wide resblock shapes): D staging and
-// all per-iteration overhead (advance, loop control, barriers) amortize
-// over KT x the MFMA work; A gather state is per (ktile, instr) slot.
-template <int NW = 4, int WBN = 64, int KT = 1>
+template <int WBN>
 __global__ __launch_bounds__(NW * 64) void wgrad_glds_kernel(WgradParams p) {
   constexpr int API = 16 / NW;        // A glds instructions per wave
-  constexpr int AT = KT * API;        // gather slots per wave
   constexpr int DCH = WBN / 8;        // 16-B chunks per D row
   constexpr int DRPI = 64 / DCH;      // D rows per glds instruction
   constexpr int TDI = (WG_BM * DCH) / 64;   // D glds instructions total
   constexpr int DPI = TDI >= NW ? TDI / NW : 1;  // per wave (maybe idle)
-  // n-fragments per wave: the 4-wave/128-n config packs 4x4 fragments
-  // per wave (32 MFMAs per tr-read set) halving LDS re-read redundancy
-  constexpr int NFW = (NW == 4 && WBN == 128) ? 4 : (WBN >= 32 ? 2 : 1);
+  constexpr int NFW = WBN >= 32 ? 2 : 1;    // n-fragments per wave
   constexpr int NWCW = WBN / (NFW * 16);    // wave-grid columns
   constexpr int KF = (WG_BK / (NW / NWCW)) / 16;  // k-fragments per wave
   extern __shared__ __attribute__((aligned(16))) char wg_smem_raw[];
-  auto& sm = *reinterpret_cast<WgSmemT<WBN, KT>*>(wg_smem_raw);
+  auto& sm = *reinterpret_cast<WgSmemT<WBN>*>(wg_smem_raw);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = tid >> 6;
   const int wbid = xcd_chunk(blockIdx.x, gridDim.x);
-  const int pairs = p.ktiles / KT;    // host guarantees p.ktiles % KT == 0
-  const int ktp = wbid % pairs;
-  const int kt = ktp * KT;            // first k-tile of this block
-  const int nt = (wbid / pairs) % p.ntiles;
-  const int sl = wbid / (pairs * p.ntiles);
+  const int kt = wbid % p.ktiles;
+  const int nt = (wbid / p.ktiles) % p.ntiles;
+  const int sl = wbid / (p.ktiles * p.ntiles);
   const long k0 = (long)kt * WG_BK;
   const int n0 = nt * WBN;
   const long mstart = sl * p.mchunks_per_slice * WG_BM;
@@ -1473,11 +1311,9 @@ __global__ __launch_bounds__(NW * 64) void wgrad_glds_kernel(WgradParams p) {
     // wgrad_reduce sums every chunk, and at::empty memory is dirty
     // (this was a real bug: reused allocator pages leaked garbage into
     // dw at shapes where slices * mchunks_per_slice overshot M)
-    for (int t = 0; t < KT; ++t) {
-      long chunk = (((long)sl * p.ktiles + kt + t) * p.ntiles + nt) *
-                   ((long)WBN * WG_BK);
-      for (int i = tid; i < WBN * WG_BK; i += NW * 64) p.ws[chunk + i] = 0.f;
-    }
+    long chunk = (((long)sl * p.ktiles + kt) * p.ntiles + nt) *
+                 ((long)WBN * WG_BK);
+    for (int i = tid; i < WBN * WG_BK; i += NW * 64) p.ws[chunk + i] = 0.f;
     return;
   }
 
@@ -1488,23 +1324,19 @@ __global__ __launch_bounds__(NW * 64) void wgrad_glds_kernel(WgradParams p) {
 
   // ---- per-lane gather identities ----
   // A: 16 instrs: instr i covers rows i*4..i*4+3; per-wave share = API
-  int a_row[AT], a_ci[AT], a_dkh[AT], a_dkw[AT];
-  bool a_kv[AT];
+  int a_row[API], a_ci[API], a_dkh[API], a_dkw[API];
+  bool a_kv[API];
   #pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    #pragma unroll
-    for (int j = 0; j < API; ++j) {
-      int sidx = t * API + j;
-      int row = (w * API + j) * 4 + (lane >> 4);
-      int cb = ((lane & 15) * 16) ^ AXOR(row);
-      long k = k0 + (long)t * WG_BK + cb / 2;
-      a_row[sidx] = row;
-      a_kv[sidx] = k < p.KTOT;
-      int tap = a_kv[sidx] ? (int)(k / p.Cin) : 0;
-      a_ci[sidx] = (int)(k - (long)tap * p.Cin);
-      a_dkh[sidx] = tap / p.KW;
-      a_dkw[sidx] = tap - a_dkh[sidx] * p.KW;
-    }
+  for (int j = 0; j < API; ++j) {
+    int row = (w * API + j) * 4 + (lane >> 4);
+    int cb = ((lane & 15) * 16) ^ AXOR(row);
+    long k = k0 + cb / 2;
+    a_row[j] = row;
+    a_kv[j] = k < p.KTOT;
+    int tap = a_kv[j] ? (int)(k / p.Cin) : 0;
+    a_ci[j] = (int)(k - (long)tap * p.Cin);
+    a_dkh[j] = tap / p.KW;
+    a_dkw[j] = tap - a_dkh[j] * p.KW;
   }
   // D: instr i covers DRPI rows; per-wave share = DPI
   const bool dw_on = w * DPI < TDI;  // waves beyond TDI stage no D
@@ -1523,9 +1355,9 @@ __global__ __launch_bounds__(NW * 64) void wgrad_glds_kernel(WgradParams p) {
   // only at image borders / batch wraps (O(1/OH) of steps).
   const unsigned C2 = (unsigned)p.Cin * 2;
   const unsigned WC2 = (unsigned)p.W * C2;
-  int a_ow[AT], a_oh[AT], a_b[AT], a_ih[AT], a_iw[AT];
-  unsigned avo[AT];
-  bool ainb[AT], avalid[AT], a_iw_ok[AT];
+  int a_ow[API], a_oh[API], a_b[API], a_ih[API], a_iw[API];
+  unsigned avo[API];
+  bool ainb[API], avalid[API], a_iw_ok[API];
   unsigned dvo[DPI];
 
   auto full_a = [&](int j) {
@@ -1543,7 +1375,7 @@ __global__ __launch_bounds__(NW * 64) void wgrad_glds_kernel(WgradParams p) {
   };
 
   #pragma unroll
-  for (int j = 0; j < AT; ++j) {
+  for (int j = 0; j < API; ++j) {
     long m = mstart + a_row[j];
     a_ow[j] = (int)(m % p.OW);
     int t = (int)(m / p.OW);
@@ -1572,7 +1404,7 @@ __global__ __launch_bounds__(NW * 64) void wgrad_glds_kernel(WgradParams p) {
       // exec-masked path (1/OH of steps) — this was the 20-mult-per-iter
       // hot spot the compiler was predicating on every iteration.
       #pragma unroll
-      for (int j = 0; j < AT; ++j) {
+      for (int j = 0; j < API; ++j) {
         bool rare = (++a_oh[j] >= p.OH);
         if (!rare) {
           int ih = a_ih[j] + p.stride;
@@ -1594,7 +1426,7 @@ __global__ __launch_bounds__(NW * 64) void wgrad_glds_kernel(WgradParams p) {
       }
     } else {
       #pragma unroll
-      for (int j = 0; j < AT; ++j) {
+      for (int j = 0; j < API; ++j) {
         int ow0 = a_ow[j], oh0 = a_oh[j], b0 = a_b[j];
         a_ow[j] += WG_BM;
         while (a_ow[j] >= p.OW) { a_ow[j] -= p.OW; ++a_oh[j]; }
@@ -1622,17 +1454,11 @@ __global__ __launch_bounds__(NW * 64) void wgrad_glds_kernel(WgradParams p) {
   // straight from the folded avo/dvo registers.
   auto stage = [&](int buf, long ms, bool tail) {
     #pragma unroll
-    for (int t = 0; t < KT; ++t) {
-      #pragma unroll
-      for (int j = 0; j < API; ++j) {
-        int sidx = t * API + j;
-        unsigned vo = (!tail || ms + a_row[sidx] < p.M) ? avo[sidx]
-                                                        : 0xFF000000u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rx, (__attribute__((address_space(3))) void*)
-                &sm.A[buf][t * (WG_BM * WG_BK) + (w * API + j) * 512],
-            16, vo, 0, 0, 0);
-      }
+    for (int j = 0; j < API; ++j) {
+      unsigned vo = (!tail || ms + a_row[j] < p.M) ? avo[j] : 0xFF000000u;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          rx, (__attribute__((address_space(3))) void*)&sm.A[buf][(w * API + j) * 512],
+          16, vo, 0, 0, 0);
     }
     if (dw_on) {
       #pragma unroll
@@ -1645,7 +1471,7 @@ __global__ __launch_bounds__(NW * 64) void wgrad_glds_kernel(WgradParams p) {
     }
   };
 
-  v4f acc[KT][KF][NFW] = {};
+  v4f acc[KF][NFW] = {};
   const int wr = w / NWCW, wc = w % NWCW;
   const int wk0 = wr * (KF * 16), wn0 = wc * (NFW * 16);
   const int fr = lane & 15, fg = lane >> 4;
@@ -1702,42 +1528,35 @@ __global__ __launch_bounds__(NW * 64) void wgrad_glds_kernel(WgradParams p) {
         bfr[nf] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
       }
       // A fragments: MFMA row = weight-k col0+fr, reduce elems = m
+      v8bf a[KF];
       #pragma unroll
-      for (int t = 0; t < KT; ++t) {
-        const char* At = Ab + t * (WG_BM * WG_BK * 2);
-        v8bf a[KF];
-        #pragma unroll
-        for (int kf = 0; kf < KF; ++kf) {
-          v4bfx lo = tr16_read(At + kk * 256 + a_base[kf][0]);
-          v4bfx hi = tr16_read(At + kk * 256 + a_base[kf][1]);
-          a[kf] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-        #pragma unroll
-        for (int kf = 0; kf < KF; ++kf)
-          #pragma unroll
-          for (int nf = 0; nf < NFW; ++nf)
-            acc[t][kf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a[kf], bfr[nf], acc[t][kf][nf], 0, 0, 0);
+      for (int kf = 0; kf < KF; ++kf) {
+        v4bfx lo = tr16_read(Ab + kk * 256 + a_base[kf][0]);
+        v4bfx hi = tr16_read(Ab + kk * 256 + a_base[kf][1]);
+        a[kf] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
       }
+      #pragma unroll
+      for (int kf = 0; kf < KF; ++kf)
+        #pragma unroll
+        for (int nf = 0; nf < NFW; ++nf)
+          acc[kf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a[kf], bfr[nf], acc[kf][nf], 0, 0, 0);
     }
     __syncthreads();
   }
 
   // slab store (no atomics): chunk layout [WBN][WG_BK], float4 rows
+  const long chunk = (((long)sl * p.ktiles + kt) * p.ntiles + nt) *
+                     ((long)WBN * WG_BK);
   #pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    long chunk = (((long)sl * p.ktiles + kt + t) * p.ntiles + nt) *
-                 ((long)WBN * WG_BK);
+  for (int nf = 0; nf < NFW; ++nf) {
+    int nl = wn0 + nf * 16 + fr;
+    if (nl >= WBN) continue;
     #pragma unroll
-    for (int nf = 0; nf < NFW; ++nf) {
-      int nl = wn0 + nf * 16 + fr;
-      if (nl >= WBN) continue;
-      #pragma unroll
-      for (int kf = 0; kf < KF; ++kf) {
-        int kl = wk0 + kf * 16 + fg * 4;
-        *(float4*)&p.ws[chunk + (long)nl * WG_BK + kl] =
-            *(const float4*)&acc[t][kf][nf];
-      }
+    for (int kf = 0; kf < KF; ++kf) {
+      int kl = wk0 + kf * 16 + fg * 4;
+      *(float4*)&p.ws[chunk + (long)nl * WG_BK + kl] =
+          *(const float4*)&acc[kf][nf];
     }
   }
 }
@@ -1844,112 +1663,49 @@ static void launch_conv_s(const ConvParams& p, dim3 grid, hipStream_t stream) {
   }
 }
 
-static int conv_nw() {
-  static int v = []() {
-    const char* e = getenv("CYG_CONV_NW");
-    return e ? atoi(e) : 8;
-  }();
-  return v;
+// n-tile width of the glds kernels: the one rule shared by the plain glds
+// launch, the phased convT launch and conv2d_wgrad.
+static int conv_ntile(int Cout) {
+  if (Cout <= 16) return 16;  // tiny-N (the 1-8 channel heads, padded to 8)
+  // wider n-tile: 1.5x arithmetic intensity for Cout >= 128 layers
+  return (Cout % 128) == 0 ? 128 : 64;
 }
 
-static int conv_bn() {
-  static int v = []() {
-    const char* e = getenv("CYG_CONV_BN");
-    return e ? atoi(e) : 128;
-  }();
-  return v;
-}
-
-template <bool IS_CONVT, int STRIDE, int NBUF, int NW, int BNT,
-          bool PHASED = false>
-static void launch_one_glds(const ConvParams& p, dim3 grid,
-                            hipStream_t stream) {
-  constexpr size_t SMB = sizeof(ConvSmemT<NBUF, BNT>);
+template <bool IS_CONVT, int STRIDE, int BNT, bool PHASED = false>
+static void launch_one_glds(const ConvParams& p, hipStream_t stream) {
+  constexpr size_t SMB = sizeof(ConvSmemT<BNT>);
   static bool init = []() {
     hipFuncSetAttribute(
-        (const void*)(conv_glds_kernel<IS_CONVT, STRIDE, NBUF, NW, BNT,
-                                       PHASED>),
+        (const void*)(conv_glds_kernel<IS_CONVT, STRIDE, BNT, PHASED>),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMB);
     return true;
   }();
   (void)init;
-  hipLaunchKernelGGL(
-      (conv_glds_kernel<IS_CONVT, STRIDE, NBUF, NW, BNT, PHASED>), grid,
-      dim3(NW * 64), SMB, stream, p);
+  hipLaunchKernelGGL((conv_glds_kernel<IS_CONVT, STRIDE, BNT, PHASED>),
+                     dim3((long)p.mtiles * p.ntiles), dim3(NW * 64), SMB,
+                     stream, p);
   hipError_t err = hipGetLastError();
-  TORCH_CHECK(err == hipSuccess, "conv_glds launch failed (NW=", NW,
-              " BNT=", BNT, " PHASED=", PHASED, "): ",
-              hipGetErrorString(err));
+  TORCH_CHECK(err == hipSuccess, "conv_glds launch failed (BNT=", BNT,
+              " PHASED=", PHASED, "): ", hipGetErrorString(err));
+}
+
+template <bool IS_CONVT, int BNT>
+static void launch_glds_s(const ConvParams& p, hipStream_t stream) {
+  switch (p.stride) {
+    case 1: launch_one_glds<IS_CONVT, 1, BNT>(p, stream); break;
+    case 2: launch_one_glds<IS_CONVT, 2, BNT>(p, stream); break;
+    default: launch_one_glds<IS_CONVT, 0, BNT>(p, stream);
+  }
 }
 
 template <bool IS_CONVT>
-static void launch_glds_s(const ConvParams& p, dim3 grid, hipStream_t stream) {
-  if constexpr (!IS_CONVT) {
-    // Halo-tiled head kernel: correct but still 137us vs the BN16
-    // implicit-GEMM's 122us on the 7x7 head (see NOTES.md for the
-    // measured iteration trail); off by default pending round-2 work.
-    static const bool use_halo = []() {
-      const char* e = getenv("CYG_HALO");
-      return e && atoi(e) != 0;
-    }();
-    if (use_halo && p.Cout == 8 && p.stride == 1 && p.Cin == 64) {
-      // halo-tiled direct kernel for the tiny-Cout heads (see kernel doc)
-      const int CW = HB_BM + p.KW - 1;
-      const int xgr = p.KH * CW * 9;       // 9 slots/pixel (bank spread)
-      const int xgr_pad = ((xgr + 511) / 512) * 512;
-      const size_t smb = (size_t)xgr_pad * 16;
-      if (smb <= 150 * 1024) {
-        static bool init = []() {
-          hipFuncSetAttribute((const void*)(conv_halo_kernel<8>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              150 * 1024);
-          return true;
-        }();
-        (void)init;
-        const int tiles_w = (p.OW + HB_BM - 1) / HB_BM;
-        dim3 gh((long)p.B * p.OH * tiles_w);
-        hipLaunchKernelGGL((conv_halo_kernel<8>), gh, dim3(512), smb,
-                           stream, p);
-        hipError_t err = hipGetLastError();
-        TORCH_CHECK(err == hipSuccess, "conv_halo launch failed: ",
-                    hipGetErrorString(err));
-        return;
-      }
-    }
-  }
-  if (p.Cout <= 16) {
-    // tiny-N (the 1-8 channel heads, padded to 8): 16-wide n-tiles
-    ConvParams q = p;
-    q.ntiles = (p.Cout + 15) / 16;
-    dim3 g2((long)q.mtiles * q.ntiles);
-    switch (p.stride) {
-      case 1: launch_one_glds<IS_CONVT, 1, 2, 8, 16>(q, g2, stream); return;
-      case 2: launch_one_glds<IS_CONVT, 2, 2, 8, 16>(q, g2, stream); return;
-      default: launch_one_glds<IS_CONVT, 0, 2, 8, 16>(q, g2, stream); return;
-    }
-  }
-  if (conv_nw() == 8 && conv_bn() == 128 && (p.Cout % 128) == 0) {
-    // wider n-tile: 1.5x arithmetic intensity for Cout >= 128 layers
-    ConvParams q = p;
-    q.ntiles = (p.Cout + 127) / 128;
-    dim3 g2((long)q.mtiles * q.ntiles);
-    switch (p.stride) {
-      case 1: launch_one_glds<IS_CONVT, 1, 2, 8, 128>(q, g2, stream); return;
-      case 2: launch_one_glds<IS_CONVT, 2, 2, 8, 128>(q, g2, stream); return;
-      default: launch_one_glds<IS_CONVT, 0, 2, 8, 128>(q, g2, stream); return;
-    }
-  }
-  if (conv_nw() == 8) {
-    switch (p.stride) {
-      case 1: launch_one_glds<IS_CONVT, 1, 2, 8, 64>(p, grid, stream); return;
-      case 2: launch_one_glds<IS_CONVT, 2, 2, 8, 64>(p, grid, stream); return;
-      default: launch_one_glds<IS_CONVT, 0, 2, 8, 64>(p, grid, stream); return;
-    }
-  }
-  switch (p.stride) {
-    case 1: launch_one_glds<IS_CONVT, 1, 2, 4, 64>(p, grid, stream); break;
-    case 2: launch_one_glds<IS_CONVT, 2, 2, 4, 64>(p, grid, stream); break;
-    default: launch_one_glds<IS_CONVT, 0, 2, 4, 64>(p, grid, stream);
+static void launch_glds(ConvParams p, hipStream_t stream) {
+  const int bnt = conv_ntile(p.Cout);
+  p.ntiles = cdiv(p.Cout, bnt);
+  switch (bnt) {
+    case 16: launch_glds_s<IS_CONVT, 16>(p, stream); break;
+    case 128: launch_glds_s<IS_CONVT, 128>(p, stream); break;
+    default: launch_glds_s<IS_CONVT, 64>(p, stream);
   }
 }
 
@@ -1967,7 +1723,7 @@ static bool phased_eligible(const ConvParams& p, bool is_convt) {
 
 // InstanceNorm slabs from the conv epilogue: number of slabs per sample
 // this call can emit (0 = not eligible; the norm then runs in_reduce).
-// Eligible = conv_glds_kernel runs it with 64/128-wide n-tiles and every
+// Eligible = the kernel runs it with 64/128-wide n-tiles and every
 // 128-row M-tile lies inside one sample: OH*OW % 128 == 0 for the plain
 // row order; for the phased convT the rows of one parity class of one
 // sample are contiguous, so (OH/2)*(OW/2) % 128 == 0 (4 classes per
@@ -1986,50 +1742,45 @@ static int stats_cap() {
   return cap;
 }
 
-static int stats_slabs(const ConvParams& p, bool is_convt, int* tps) {
+// fp8: conv_fp8_kernel always runs 128x64 tiles in plain row order and its
+// wrapper checks its own offset limits, so neither the phased regrouping
+// nor the glds-eligibility term applies; everything else is shared.
+static int stats_slabs(const ConvParams& p, bool is_convt, bool fp8,
+                       int* tps) {
   const int cap = stats_cap();
-  if (cap <= 0 || !glds_eligible(p) || p.Cout <= 16 || (p.Cout % 8) != 0)
-    return 0;
-  long per, ns;
-  if (phased_eligible(p, is_convt)) {
-    per = (long)(p.OH / 2) * (p.OW / 2);
-    ns = 4 * (per / BM);
-  } else {
-    per = (long)p.OH * p.OW;
-    ns = per / BM;
-  }
+  if (cap <= 0 || p.Cout <= 16 || (p.Cout % 8) != 0) return 0;
+  if (!fp8 && !glds_eligible(p)) return 0;
+  const bool phased = !fp8 && phased_eligible(p, is_convt);
+  const long per = phased ? (long)(p.OH / 2) * (p.OW / 2)
+                          : (long)p.OH * p.OW;
+  const long ns = (phased ? 4 : 1) * (per / BM);
   if (per % BM != 0 || ns > cap) return 0;
   *tps = (int)(per / BM);
   return (int)ns;
 }
 
 static void launch_conv(const ConvParams& p, bool is_convt, hipStream_t stream) {
-  dim3 grid(p.mtiles * p.ntiles);
-  bool aligned = (p.Cin % 8) == 0;
-  bool glds_ok = glds_eligible(p);
   if (phased_eligible(p, is_convt)) {
-    // phase-decomposed: 4 phase classes, only matching-parity taps
+    // phase-decomposed: 4 phase classes, only matching-parity taps. The
+    // phased kernel has no 16-wide form; tiny Cout takes the 64-wide tile.
     ConvParams q = p;
     long Mp = (long)q.B * (q.OH / 2) * (q.OW / 2);
     q.mtiles = 4 * cdiv(Mp, BM);
-    if (conv_nw() == 8 && conv_bn() == 128 && (q.Cout % 128) == 0) {
-      q.ntiles = (q.Cout + 127) / 128;
-      dim3 g2((long)q.mtiles * q.ntiles);
-      launch_one_glds<true, 2, 2, 8, 128, true>(q, g2, stream);
-    } else if (conv_nw() == 8) {
-      dim3 g2((long)q.mtiles * q.ntiles);
-      launch_one_glds<true, 2, 2, 8, 64, true>(q, g2, stream);
+    if (conv_ntile(q.Cout) == 128) {
+      q.ntiles = cdiv(q.Cout, 128);
+      launch_one_glds<true, 2, 128, true>(q, stream);
     } else {
-      dim3 g2((long)q.mtiles * q.ntiles);
-      launch_one_glds<true, 2, 2, 4, 64, true>(q, g2, stream);
+      launch_one_glds<true, 2, 64, true>(q, stream);
     }
     return;
   }
-  if (glds_ok) {
-    if (is_convt) launch_glds_s<true>(p, grid, stream);
-    else launch_glds_s<false>(p, grid, stream);
+  if (glds_eligible(p)) {
+    if (is_convt) launch_glds<true>(p, stream);
+    else launch_glds<false>(p, stream);
     return;
   }
+  dim3 grid(p.mtiles * p.ntiles);
+  bool aligned = (p.Cin % 8) == 0;
   if (is_convt) {
     if (aligned) launch_conv_s<true, true>(p, grid, stream);
     else launch_conv_s<true, false>(p, grid, stream);
@@ -2039,6 +1790,8 @@ static void launch_conv(const ConvParams& p, bool is_convt, hipStream_t stream) 
   }
 }
 
+// x/w may be bf16 or (fp8 conv) e4m3 byte tensors: only their sizes and
+// base pointers are read. The caller sets pt/pl/reflect (and dq/dqb).
 static ConvParams fill_common(const at::Tensor& x, const at::Tensor& w,
                               const c10::optional<at::Tensor>& bias,
                               at::Tensor& y, int stride, int act, double slope) {
@@ -2067,22 +1820,29 @@ static void check_conv_inputs(const at::Tensor& x, const at::Tensor& w) {
   TORCH_CHECK(w.size(3) == x.size(3), "conv: Cin mismatch");
 }
 
-// want_stats: also return the InstanceNorm partial slabs {y, psum, psq}
-// ([NS,B,Cout] fp32) when the call is eligible (stats_slabs); {y} otherwise.
-static std::vector<at::Tensor> run_fwd(ConvParams& p, at::Tensor& y,
-                                       bool is_convt, bool want_stats) {
-  std::vector<at::Tensor> out{y};
+// want_stats: when the call is eligible (stats_slabs), allocate the
+// InstanceNorm partial slabs ([NS,B,Cout] fp32 each), point p at them and
+// append {psum, psq} to out = {y}. Returns the slab count (0 = none).
+static int add_stats(ConvParams& p, bool is_convt, bool fp8, bool want_stats,
+                     std::vector<at::Tensor>& out) {
   int tps = 0;
-  int ns = want_stats ? stats_slabs(p, is_convt, &tps) : 0;
+  const int ns = want_stats ? stats_slabs(p, is_convt, fp8, &tps) : 0;
   if (ns > 0) {
     auto ps = at::empty({2, ns, (long)p.B, (long)p.Cout},
-                        y.options().dtype(at::kFloat));
+                        out[0].options().dtype(at::kFloat));
     p.psum = (float*)ps.mutable_data_ptr();
     p.psq = p.psum + (long)ns * p.B * p.Cout;
     p.tps = tps;
     out.push_back(ps[0]);
     out.push_back(ps[1]);
   }
+  return ns;
+}
+
+static std::vector<at::Tensor> run_fwd(ConvParams& p, at::Tensor& y,
+                                       bool is_convt, bool want_stats) {
+  std::vector<at::Tensor> out{y};
+  add_stats(p, is_convt, false, want_stats, out);
   launch_conv(p, is_convt, at::cuda::getCurrentCUDAStream());
   return out;
 }
@@ -2188,6 +1948,38 @@ at::Tensor convt2d_dgrad(at::Tensor dy, at::Tensor wt, int64_t IH, int64_t IW,
   return dx;
 }
 
+// split M so total blocks ≈ 2-4x CU count (CYG_WG_BLOCKS to sweep)
+struct WgSplit { int slices; long mchunks_per_slice; };  // chunks of 64 rows
+static WgSplit wgrad_split(long M, int ktiles, int ntiles) {
+  static const int tgt_blocks = []() {
+    const char* e = getenv("CYG_WG_BLOCKS");
+    return e ? atoi(e) : 512;
+  }();
+  const long mchunks = (M + WG_BM - 1) / WG_BM;
+  const int target = std::max<long>(1, tgt_blocks / ((long)ktiles * ntiles));
+  const int slices = (int)std::min<long>(mchunks, target);
+  const long per = (mchunks + slices - 1) / slices;
+  // re-derive so no slice is empty (ceil division can overshoot)
+  return {(int)((mchunks + per - 1) / per), per};
+}
+
+template <int WBN>
+static void launch_wgrad_glds(const WgradParams& p, dim3 grid,
+                              hipStream_t stream) {
+  constexpr size_t SMB = sizeof(WgSmemT<WBN>);
+  if constexpr (WBN == 128) {  // the 64 KiB image needs the opt-in
+    static bool init = []() {
+      hipFuncSetAttribute((const void*)(wgrad_glds_kernel<128>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)SMB);
+      return true;
+    }();
+    (void)init;
+  }
+  hipLaunchKernelGGL((wgrad_glds_kernel<WBN>), grid, dim3(NW * 64), SMB,
+                     stream, p);
+}
+
 at::Tensor conv2d_wgrad(at::Tensor x, at::Tensor dy, int64_t KH, int64_t KW,
                         int64_t stride, int64_t pt, int64_t pl, bool reflect) {
   TORCH_CHECK(x.is_cuda() && dy.is_cuda() && x.is_contiguous() && dy.is_contiguous());
@@ -2202,123 +1994,41 @@ at::Tensor conv2d_wgrad(at::Tensor x, at::Tensor dy, int64_t KH, int64_t KW,
   p.reflect = reflect ? 1 : 0;
   p.M = (long)p.B * p.OH * p.OW;
   p.KTOT = (long)KH * KW * p.Cin;
+  const bool glds_ok = (p.Cin % 8) == 0 && (p.Cout % 8) == 0 &&
+                       (long)p.B * p.H * p.W * p.Cin * 2 < (1L << 31) &&
+                       p.M * p.Cout * 2 < (1L << 31);
+  // the unaligned-channel fallback (wgrad_kernel) has WG_BN-wide tiles only
+  const int wbn = glds_ok ? conv_ntile(p.Cout) : WG_BN;
   p.ktiles = cdiv(p.KTOT, WG_BK);
-  p.ntiles = cdiv(p.Cout, WG_BN);
-  // split M so total blocks ≈ 2-4x CU count (CYG_WG_BLOCKS to sweep)
-  long mchunks = (p.M + WG_BM - 1) / WG_BM;
-  static int tgt_blocks = []() {
-    const char* e = getenv("CYG_WG_BLOCKS");
-    return e ? atoi(e) : 512;
-  }();
-  int target = std::max<long>(1, tgt_blocks / ((long)p.ktiles * p.ntiles));
-  int slices = (int)std::min<long>(mchunks, target);
-  p.mchunks_per_slice = (mchunks + slices - 1) / slices;
-  // re-derive so no slice is empty (ceil division can overshoot)
-  p.slices = (int)((mchunks + p.mchunks_per_slice - 1) / p.mchunks_per_slice);
+  p.ntiles = cdiv(p.Cout, wbn);
+  const WgSplit split = wgrad_split(p.M, p.ktiles, p.ntiles);
+  p.slices = split.slices;
+  p.mchunks_per_slice = split.mchunks_per_slice;
   dim3 grid((long)p.ktiles * p.ntiles * p.slices);
-  bool glds_ok = (p.Cin % 8) == 0 && (p.Cout % 8) == 0 &&
-                 (long)p.B * p.H * p.W * p.Cin * 2 < (1L << 31) &&
-                 p.M * p.Cout * 2 < (1L << 31);
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (glds_ok) {
-    auto dw = at::empty({p.Cout, (long)KH, (long)KW, p.Cin},
+  if (!glds_ok) {
+    auto dw = at::zeros({p.Cout, (long)KH, (long)KW, p.Cin},
                         x.options().dtype(at::kFloat));
     p.dw = (float*)dw.mutable_data_ptr();
-    int wbn = (conv_nw() == 8 && conv_bn() == 128 && (p.Cout % 128) == 0)
-                  ? 128 : WG_BN;
-    if (p.Cout <= 16) wbn = 16;  // tiny-N heads: 16-wide n-tiles
-    if (wbn != WG_BN) {
-      p.ntiles = (p.Cout + wbn - 1) / wbn;
-      // re-balance the split-M slices for the changed tile count
-      long mchunks = (p.M + WG_BM - 1) / WG_BM;
-      static int tgt2 = []() {
-        const char* e = getenv("CYG_WG_BLOCKS");
-        return e ? atoi(e) : 512;
-      }();
-      int target = std::max<long>(1, tgt2 / ((long)p.ktiles * p.ntiles));
-      p.slices = (int)std::min<long>(mchunks, target);
-      p.mchunks_per_slice = (mchunks + p.slices - 1) / p.slices;
-      p.slices = (int)((mchunks + p.mchunks_per_slice - 1) /
-                       p.mchunks_per_slice);
-      grid = dim3((long)p.ktiles * p.ntiles * p.slices);
-    }
-    static int wg_nw = []() {
-      const char* e = getenv("CYG_WG_NW");
-      return e ? atoi(e) : 8;
-    }();
-    static int wg_kt = []() {
-      // measured NEGATIVE (K3 wgrad 65.8 vs 45.2 us; bench 300 vs 326):
-      // the 96 KB LDS footprint drops occupancy to 1 block/CU and the
-      // lost latency hiding dwarfs the amortized staging. CYG_WG_KT=2
-      // to re-enable.
-      const char* e = getenv("CYG_WG_KT");
-      return e ? atoi(e) : 1;
-    }();
-    // 2 k-tiles per block (wide shapes with an even k-tile count):
-    // re-balance the split-M slices for the halved block count
-    bool kt2 = wbn == 128 && wg_nw == 8 && wg_kt == 2 &&
-               (p.ktiles % 2) == 0;
-    if (kt2) {
-      long mchunks2 = (p.M + WG_BM - 1) / WG_BM;
-      int pairs = p.ktiles / 2;
-      int target2 =
-          std::max<long>(1, tgt_blocks / ((long)pairs * p.ntiles));
-      p.slices = (int)std::min<long>(mchunks2, target2);
-      p.mchunks_per_slice = (mchunks2 + p.slices - 1) / p.slices;
-      p.slices = (int)((mchunks2 + p.mchunks_per_slice - 1) /
-                       p.mchunks_per_slice);
-      grid = dim3((long)pairs * p.ntiles * p.slices);
-    }
-    auto ws = at::empty({(long)p.slices * p.ktiles * p.ntiles *
-                         wbn * WG_BK},
-                        x.options().dtype(at::kFloat));
-    p.ws = (float*)ws.mutable_data_ptr();
-    if (wbn == 128) {
-      constexpr size_t SMB = sizeof(WgSmemT<128>);
-      constexpr size_t SMB2 = sizeof(WgSmemT<128, 2>);
-      static bool init = []() {
-        hipFuncSetAttribute((const void*)(wgrad_glds_kernel<8, 128>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)SMB);
-        hipFuncSetAttribute((const void*)(wgrad_glds_kernel<4, 128>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)SMB);
-        hipFuncSetAttribute((const void*)(wgrad_glds_kernel<8, 128, 2>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)SMB2);
-        return true;
-      }();
-      (void)init;
-      if (kt2)
-        hipLaunchKernelGGL((wgrad_glds_kernel<8, 128, 2>), grid, dim3(512),
-                           SMB2, stream, p);
-      else if (wg_nw == 4)
-        hipLaunchKernelGGL((wgrad_glds_kernel<4, 128>), grid, dim3(256), SMB,
-                           stream, p);
-      else
-        hipLaunchKernelGGL((wgrad_glds_kernel<8, 128>), grid, dim3(512), SMB,
-                           stream, p);
-    } else if (wbn == 16) {
-      hipLaunchKernelGGL((wgrad_glds_kernel<8, 16>), grid, dim3(512),
-                         sizeof(WgSmemT<16>), stream, p);
-    } else if (conv_nw() == 8) {
-      hipLaunchKernelGGL((wgrad_glds_kernel<8, 64>), grid, dim3(512),
-                         sizeof(WgSmemT<64>), stream, p);
-    } else {
-      hipLaunchKernelGGL((wgrad_glds_kernel<4, 64>), grid, dim3(NTHREADS),
-                         sizeof(WgSmemT<64>), stream, p);
-    }
-    long total = (long)p.ktiles * WG_BK * p.ntiles * wbn;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total, 256)),
-                       dim3(256), 0, stream,
-                       (const float*)ws.const_data_ptr(), p.dw, p.KTOT,
-                       p.Cout, p.ktiles, p.ntiles, p.slices, wbn);
+    hipLaunchKernelGGL(wgrad_kernel, grid, dim3(NTHREADS), 0, stream, p);
     return dw;
   }
-  auto dw = at::zeros({p.Cout, (long)KH, (long)KW, p.Cin},
+  auto dw = at::empty({p.Cout, (long)KH, (long)KW, p.Cin},
                       x.options().dtype(at::kFloat));
   p.dw = (float*)dw.mutable_data_ptr();
-  hipLaunchKernelGGL(wgrad_kernel, grid, dim3(NTHREADS), 0, stream, p);
+  auto ws = at::empty({(long)p.slices * p.ktiles * p.ntiles * wbn * WG_BK},
+                      x.options().dtype(at::kFloat));
+  p.ws = (float*)ws.mutable_data_ptr();
+  switch (wbn) {
+    case 16: launch_wgrad_glds<16>(p, grid, stream); break;
+    case 128: launch_wgrad_glds<128>(p, grid, stream); break;
+    default: launch_wgrad_glds<64>(p, grid, stream);
+  }
+  long total = (long)p.ktiles * WG_BK * p.ntiles * wbn;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total, 256)),
+                     dim3(256), 0, stream,
+                     (const float*)ws.const_data_ptr(), p.dw, p.KTOT,
+                     p.Cout, p.ktiles, p.ntiles, p.slices, wbn);
   return dw;
 }
 
@@ -2366,18 +2076,7 @@ void amax_roll(at::Tensor arena, int64_t n) {
                      (float*)arena.mutable_data_ptr(), (int)n, cap);
 }
 
-// conv_fp8_kernel always runs 128x64 tiles in plain row order, so the
-// stats_slabs rule reduces to: every M-tile inside one sample, the slab
-// count under the same cap, and the same Cout limits.
-static int stats_slabs_fp8(const ConvParams& p) {
-  const int cap = stats_cap();
-  if (cap <= 0 || p.Cout <= 16 || (p.Cout % 8) != 0) return 0;
-  long per = (long)p.OH * p.OW;
-  if (per % BM != 0 || per / BM > cap) return 0;
-  return (int)(per / BM);
-}
-
-// want_stats: {y, psum, psq} when stats_slabs_fp8 finds the call eligible,
+// want_stats: {y, psum, psq} when stats_slabs finds the call eligible,
 // {y} otherwise; y is the same either way.
 static std::vector<at::Tensor> conv2d_fp8_fwd_impl(
     at::Tensor xq, at::Tensor wq, at::Tensor dq, c10::optional<at::Tensor> sw,
@@ -2394,36 +2093,14 @@ static std::vector<at::Tensor> conv2d_fp8_fwd_impl(
   int OW = (W + pl + pr - KW) / stride + 1;
   auto y = at::empty({xq.size(0), OH, OW, wq.size(0)},
                      xq.options().dtype(at::kBFloat16));
-  ConvParams p{};
-  p.x = (const short*)xq.const_data_ptr();
-  p.w = (const short*)wq.const_data_ptr();
-  p.bias = bias.has_value() ? (const short*)bias->const_data_ptr() : nullptr;
+  auto p = fill_common(xq, wq, bias, y, stride, act, slope);
+  p.pt = pt; p.pl = pl; p.reflect = reflect ? 1 : 0;
   p.dq = (const float*)dq.const_data_ptr();
   p.dqb = sw.has_value() ? (const float*)sw->const_data_ptr() : nullptr;
-  p.y = (short*)y.mutable_data_ptr();
-  p.B = xq.size(0); p.H = H; p.W = W; p.Cin = xq.size(3);
-  p.OH = OH; p.OW = OW; p.Cout = wq.size(0);
-  p.KH = KH; p.KW = KW;
-  p.stride = stride; p.pt = pt; p.pl = pl;
-  p.reflect = reflect ? 1 : 0;
-  p.act = act; p.slope = (float)slope;
-  p.M = (long)p.B * OH * OW;
-  p.KTOT = (long)KH * KW * p.Cin;
-  p.mtiles = cdiv(p.M, BM);
-  p.ntiles = cdiv(p.Cout, BN);
   TORCH_CHECK((long)p.B * H * W * p.Cin < (1L << 31) &&
               (long)p.Cout * p.KTOT < (1L << 31));
   std::vector<at::Tensor> out{y};
-  const int ns = want_stats ? stats_slabs_fp8(p) : 0;
-  if (ns > 0) {
-    auto ps = at::empty({2, ns, (long)p.B, (long)p.Cout},
-                        y.options().dtype(at::kFloat));
-    p.psum = (float*)ps.mutable_data_ptr();
-    p.psq = p.psum + (long)ns * p.B * p.Cout;
-    p.tps = ns;
-    out.push_back(ps[0]);
-    out.push_back(ps[1]);
-  }
+  const int ns = add_stats(p, false, true, want_stats, out);
   auto stream = at::cuda::getCurrentCUDAStream();
   dim3 grid(p.mtiles * p.ntiles);
 #define LAUNCH_FP8(S)                                                        \
@@ -2459,151 +2136,6 @@ std::vector<at::Tensor> conv2d_fp8_fwd_stats(
     int64_t pl, int64_t pr, bool reflect, int64_t act, double slope) {
   return conv2d_fp8_fwd_impl(xq, wq, dq, sw, bias, stride, pt, pb, pl, pr,
                              reflect, act, slope, true);
-}
-
-// ---- glds probe (test aid): verify raw_ptr_buffer_load_lds semantics ----
-// lane l loads 16B from x at voff[l]; expect LDS dest = base + l*16 and
-// OOB voffsets to produce zeros.
-__global__ void glds_probe_kernel(const float* x, const unsigned* voff,
-                                  int nbytes, float* out) {
-  __shared__ float lds[128];
-  int l = threadIdx.x;  // 64 threads
-  lds[l] = -1.f; lds[64 + l] = -1.f;
-  __syncthreads();
-  auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, nbytes, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(
-      rsrc, (__attribute__((address_space(3))) void*)&lds[0], 16, voff[l], 0,
-      0, 0);
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  out[l] = lds[l];
-  out[64 + l] = lds[64 + l];
-}
-
-at::Tensor glds_probe(at::Tensor x, at::Tensor voff) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat);
-  TORCH_CHECK(voff.scalar_type() == at::kInt && voff.numel() == 64);
-  auto out = at::empty({128}, x.options());
-  hipLaunchKernelGGL(glds_probe_kernel, dim3(1), dim3(64), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     (const float*)x.const_data_ptr(),
-                     (const unsigned*)voff.const_data_ptr(),
-                     (int)(x.numel() * 4), (float*)out.mutable_data_ptr());
-  return out;
-}
-
-// ---- ds_read_b64_tr_b16 probe: identity-filled LDS, per-lane address by
-// mode; out[l*4+j] = LDS element index that lane l's element j received.
-typedef bf16r v4bf __attribute__((ext_vector_type(4)));
-typedef short v4sh __attribute__((ext_vector_type(4)));
-__global__ void tr_probe_kernel(short* out, int mode) {
-  __shared__ short lds[1024];
-  int l = threadIdx.x;
-  for (int i = l; i < 1024; i += 64) lds[i] = (short)i;
-  __syncthreads();
-  int addr;
-  switch (mode) {
-    case 0: addr = (l & 15) + (l >> 4) * 64; break;
-    case 1: addr = 0; break;
-    case 2: addr = l * 4; break;
-    default: addr = (l & 15) * 2 + (l >> 4) * 64; break;
-  }
-  auto p = (__attribute__((address_space(3))) v4bf*)(
-      (__attribute__((address_space(3))) short*)lds + addr);
-  v4bf r = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p);
-  #pragma unroll
-  for (int j = 0; j < 4; ++j) out[l * 4 + j] = ((v4sh&)r)[j];
-}
-
-at::Tensor tr_probe(int64_t mode) {
-  auto out = at::empty({256}, at::TensorOptions().dtype(at::kShort).device(at::kCUDA));
-  hipLaunchKernelGGL(tr_probe_kernel, dim3(1), dim3(64), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     (short*)out.mutable_data_ptr(), (int)mode);
-  return out;
-}
-
-// ---- MFMA layout probe (test aid): C[16,16] = A[16,32] @ Bt[16,32]^T ----
-// MX-scaled fp8 MFMA probe (round-2 prep): raw per-lane operand dump for
-// mapping the 32x32x64 f8f6f4 fragment layout empirically, exactly how
-// mfma_probe established the bf16 16x16x32 layout. Operands are the raw
-// 32 bytes each lane supplies (a/b as [64][8] int32); scale operands use
-// cbsz/blgp = 0 (e4m3 A and B) and a single scale byte broadcast.
-typedef int v8i_ __attribute__((ext_vector_type(8)));
-typedef float v16f_ __attribute__((ext_vector_type(16)));
-__global__ void mx_probe_kernel(const int* a, const int* b, float* d,
-                                int sa, int sb) {
-  int lane = threadIdx.x & 63;
-  v8i_ av = *(const v8i_*)(a + lane * 8);
-  v8i_ bv = *(const v8i_*)(b + lane * 8);
-  v16f_ acc = {};
-  acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-      av, bv, acc, 0, 0, 0, sa, 0, sb);
-  #pragma unroll
-  for (int r = 0; r < 16; ++r) d[lane * 16 + r] = acc[r];
-}
-
-// 16x16x128 scaled-fp8 probe: same raw per-lane operand dump for the
-// D[16,16] = A[16,128] @ B[128,16] fragment (v4f acc).
-__global__ void mx_probe16_kernel(const int* a, const int* b, float* d,
-                                  int sa, int sb) {
-  int lane = threadIdx.x & 63;
-  v8i_ av = *(const v8i_*)(a + lane * 8);
-  v8i_ bv = *(const v8i_*)(b + lane * 8);
-  v4f acc = {};
-  acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-      av, bv, acc, 0, 0, 0, sa, 0, sb);
-  #pragma unroll
-  for (int r = 0; r < 4; ++r) d[lane * 4 + r] = acc[r];
-}
-
-at::Tensor mx_probe16(at::Tensor a, at::Tensor b, int64_t sa, int64_t sb) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kInt &&
-              a.sizes() == at::IntArrayRef({64, 8}) &&
-              b.sizes() == at::IntArrayRef({64, 8}));
-  auto d = at::empty({64, 4}, a.options().dtype(at::kFloat));
-  hipLaunchKernelGGL(mx_probe16_kernel, dim3(1), dim3(64), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     (const int*)a.contiguous().const_data_ptr(),
-                     (const int*)b.contiguous().const_data_ptr(),
-                     (float*)d.mutable_data_ptr(), (int)sa, (int)sb);
-  return d;
-}
-
-at::Tensor mx_probe(at::Tensor a, at::Tensor b, int64_t sa, int64_t sb) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kInt &&
-              a.sizes() == at::IntArrayRef({64, 8}) &&
-              b.sizes() == at::IntArrayRef({64, 8}));
-  auto d = at::empty({64, 16}, a.options().dtype(at::kFloat));
-  hipLaunchKernelGGL(mx_probe_kernel, dim3(1), dim3(64), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     (const int*)a.contiguous().const_data_ptr(),
-                     (const int*)b.contiguous().const_data_ptr(),
-                     (float*)d.mutable_data_ptr(), (int)sa, (int)sb);
-  return d;
-}
-
-__global__ void mfma_probe_kernel(const short* a, const short* bt, float* c) {
-  int lane = threadIdx.x & 63;
-  int fr = lane & 15, fg = lane >> 4;
-  v8bf av = *(const v8bf*)(a + fr * 32 + fg * 8);
-  v8bf bv = *(const v8bf*)(bt + fr * 32 + fg * 8);
-  v4f d = {};
-  d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, d, 0, 0, 0);
-  #pragma unroll
-  for (int r = 0; r < 4; ++r) c[(fg * 4 + r) * 16 + fr] = d[r];
-}
-
-at::Tensor mfma_probe(at::Tensor a, at::Tensor bt) {
-  TORCH_CHECK(a.sizes() == at::IntArrayRef({16, 32}) &&
-              bt.sizes() == at::IntArrayRef({16, 32}));
-  auto c = at::empty({16, 16}, a.options().dtype(at::kFloat));
-  hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     (const short*)a.contiguous().const_data_ptr(),
-                     (const short*)bt.contiguous().const_data_ptr(),
-                     (float*)c.mutable_data_ptr());
-  return c;
 }
 
 }  // namespace cyg
