@@ -19,7 +19,11 @@
 //                        wgrad_reduce_kernel, no atomics
 //   wgrad_kernel         fallback for Cin % 8 != 0 or Cout % 8 != 0
 //                        (fp32 atomics over the split-M slices)
-//   reflect_fold_kernel  folds the padded-frame dgrad back over the mirrors
+//   reflect_ring_add_kernel  reflect dgrad: adds the pad ring onto the
+//                        mirrored rows/columns of dx (the gather writes the
+//                        unpadded frame itself)
+//   reflect_fold_kernel  full-frame fold of a padded-frame dgrad (fallback
+//                        path and CYG_NO_DIRECT_FOLD=1)
 //
 // GEMM view: M = B*OH*OW output pixels, N = Cout, K = KH*KW*Cin, with the
 // im2col A-tile gathered on the fly (reflection padding = a load-index
@@ -69,7 +73,26 @@ struct ConvParams {
   float* psum;
   float* psq;
   int tps;
+  // reflect dgrad straight into the unpadded frame (non-phased convT
+  // gather only; ringoff == 0 = off). The M space is still the padded
+  // frame [B,OH,OW]; rows inside the window wt <= oh < wt+wH,
+  // wl <= ow < wl+wW go to y as a [B,wH,wW,Cout] image, every other row to
+  // the compact ring image that starts ringoff elements after y
+  // (ring_index below).
+  long ringoff;
+  int wt, wl, wH, wW;
 };
+
+// Compact layout of the padded-frame pixels outside the window, per
+// sample: the rows above the window, then the rows below it (both OW
+// wide), then for each window row its left and right pieces side by side.
+// Shared by the dgrad row decode and reflect_ring_add_kernel.
+DEV int ring_index(int qh, int qw, int OH, int OW, int wt, int wl, int wH,
+                   int wW) {
+  if (qh < wt) return qh * OW + qw;
+  if (qh >= wt + wH) return (qh - wH) * OW + qw;
+  return (OH - wH) * OW + (qh - wt) * (OW - wW) + (qw < wl ? qw : qw - wW);
+}
 
 // XCD-aware block remap: hardware dispatches blockIdx round-robin over the
 // 8 XCDs, so consecutive tiles (which gather overlapping input rows) land
@@ -349,7 +372,21 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
       int b = (int)(mm / ((long)p.OW * p.OH));
       sm.rowok[r] = ok;
       sm.rowxb[r] = (unsigned)((long)b * p.H * p.W * p.Cin * 2);
-      sm.rowyb[r] = ((long)(b * p.OH + oh) * p.OW + ow) * p.Cout;
+      long yb = ((long)(b * p.OH + oh) * p.OW + ow) * p.Cout;
+      if (IS_CONVT && p.ringoff != 0) {
+        // reflect dgrad: window pixels land in the unpadded image, the
+        // rest in the ring image behind it
+        const int i = oh - p.wt, j = ow - p.wl;
+        if ((unsigned)i < (unsigned)p.wH && (unsigned)j < (unsigned)p.wW) {
+          yb = (((long)b * p.wH + i) * p.wW + j) * p.Cout;
+        } else {
+          const long rp = (long)p.OH * p.OW - (long)p.wH * p.wW;
+          yb = p.ringoff +
+               (b * rp + ring_index(oh, ow, p.OH, p.OW, p.wt, p.wl, p.wH,
+                                    p.wW)) * p.Cout;
+        }
+      }
+      sm.rowyb[r] = yb;
       if (IS_CONVT) {
         sm.rowih[r] = oh + p.pt;
         sm.rowiw[r] = ow + p.pl;
@@ -1642,9 +1679,111 @@ __global__ void reflect_fold_kernel(const short* __restrict__ dxp,
   *(v8s*)(dx + (((long)b * H + i) * W + j) * C + g * 8) = out;
 }
 
+// Up to two disjoint index intervals [a0, a0+n0) and [a1, a1+n1) with
+// a0 + n0 <= a1: the rows (or columns) of the image that have a mirror
+// source in the padded frame.
+struct Span2 { int a0, n0, a1, n1; };
+DEV int span_nth(Span2 s, int k) {      // k-th index inside
+  return k < s.n0 ? s.a0 + k : s.a1 + (k - s.n0);
+}
+DEV int span_nth_out(Span2 s, int k) {  // k-th index outside
+  if (k >= s.a0) k += s.n0;
+  if (k >= s.a1) k += s.n1;
+  return k;
+}
+
+// ---------------- reflect ring add (direct-fold dgrad) ----------------
+// The dgrad has written window pixels of the padded frame straight into
+// dx and the others into the ring image (ConvParams::ringoff). Only dx
+// pixels in a mirrored row or column (rs / cs) receive anything more; one
+// thread per 8 channels of such a pixel re-sums it in
+// reflect_fold_kernel's candidate order (rows outer, cols inner; direct,
+// low mirror, high mirror; same de-duplication), the direct term from dx
+// itself and every mirror term from the ring, rounds once and writes in
+// place. No thread reads another thread's dx pixel.
+__global__ void reflect_ring_add_kernel(short* __restrict__ dx,
+                                        const short* __restrict__ ring,
+                                        int B, int H, int W, int C,
+                                        int pt, int pb, int pl, int pr,
+                                        Span2 rs, Span2 cs) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int gpr = C / 8;
+  const int nr = rs.n0 + rs.n1, nc = cs.n0 + cs.n1;
+  const int ppb = nr * W + (H - nr) * nc;  // pixels per sample
+  long total = (long)B * ppb * gpr;
+  if (idx >= total) return;
+  int g = (int)(idx % gpr);
+  long t = idx / gpr;
+  int q = (int)(t % ppb);
+  int b = (int)(t / ppb);
+  int i, j;
+  if (q < nr * W) {
+    i = span_nth(rs, q / W);
+    j = q % W;
+  } else {
+    q -= nr * W;
+    i = span_nth_out(rs, q / nc);
+    j = span_nth(cs, q % nc);
+  }
+  int HP = H + pt + pb, WP = W + pl + pr;
+  long rp = (long)HP * WP - (long)H * W;
+  short* own = dx + (((long)b * H + i) * W + j) * C + g * 8;
+  float s[8] = {};
+  int hc[3] = {pt + i, pt - i, pt + 2 * (H - 1) - i};
+  int wc_[3] = {pl + j, pl - j, pl + 2 * (W - 1) - j};
+  #pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    int qh = hc[a];
+    if (qh < 0 || qh >= HP) continue;
+    if (a > 0 && qh == hc[0]) continue;
+    if (a == 2 && qh == hc[1]) continue;
+    if (mirror_idx(qh - pt, H) != i) continue;
+    #pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      int qw = wc_[d];
+      if (qw < 0 || qw >= WP) continue;
+      if (d > 0 && qw == wc_[0]) continue;
+      if (d == 2 && qw == wc_[1]) continue;
+      if (mirror_idx(qw - pl, W) != j) continue;
+      // a surviving mirror candidate lies outside the window
+      const short* src = (a == 0 && d == 0)
+          ? own
+          : ring + (b * rp + ring_index(qh, qw, HP, WP, pt, pl, H, W)) * C +
+                g * 8;
+      v8s v = *(const v8s*)src;
+      #pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] += b2f(v[e]);
+    }
+  }
+  v8s out;
+  #pragma unroll
+  for (int e = 0; e < 8; ++e) out[e] = f2b(s[e]);
+  *(v8s*)own = out;
+}
+
 // ================= host wrappers =================
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// A/B switches that are read on every call (a test flips them inside one
+// process): pass the getenv() result.
+static inline bool env_flag(const char* v) { return v && v[0] == '1'; }
+
+// Indices of an axis of length n that have a mirror source under reflect
+// pads (lo, hi): 1..lo from the low side, n-1-hi..n-2 from the high side
+// (reflect_fold_kernel's surviving candidates), merged where they touch.
+static Span2 mirror_span(int n, int lo, int hi) {
+  const int a0 = 1, b0 = std::min(lo, n - 1);
+  const int a1 = std::max(n - 1 - hi, 0), b1 = n - 2;
+  const int n0 = std::max(b0 - a0 + 1, 0), n1 = std::max(b1 - a1 + 1, 0);
+  if (n0 == 0) return {a1, n1, a1 + n1, 0};
+  if (n1 == 0) return {a0, n0, a0 + n0, 0};
+  if (a1 <= a0 + n0) {
+    const int a = std::min(a0, a1), b = std::max(b0, b1);
+    return {a, b - a + 1, b + 1, 0};
+  }
+  return {a0, n0, a1, n1};
+}
 
 template <bool IS_CONVT, bool ALIGNED>
 static void launch_conv_s(const ConvParams& p, dim3 grid, hipStream_t stream) {
@@ -1917,16 +2056,43 @@ at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt, int64_t H, int64_t W,
     launch_conv(p, true, stream);
     return dx;
   }
-  // reflect: dgrad into the padded frame, then fold mirrors back
+  TORCH_CHECK(wt.size(0) % 8 == 0, "reflect dgrad: Cin % 8 != 0");
   long HP = H + pt + pb, WP = W + pl + pr;
-  auto dxp = at::empty({dy.size(0), HP, WP, wt.size(0)}, dy.options());
+  // Direct fold: the gather writes window pixels of the padded frame
+  // straight into dx and only the ring around it into a side image, then
+  // reflect_ring_add_kernel adds the ring onto the mirrored rows and
+  // columns in place. glds path and stride 1 only (no model pairs reflect
+  // padding with a stride; that and the conv_gemm_kernel fallback keep the
+  // full-frame fold below). CYG_NO_DIRECT_FOLD=1, read per call, selects
+  // the full-frame fold.
+  const long B = dy.size(0), C = wt.size(0);
+  const long nimg = B * H * W * C;
+  auto dxp = at::empty({B, HP, WP, C}, dy.options());
   auto p = fill_common(dy, wt, c10::nullopt, dxp, stride, ACT_NONE, 0.0);
   p.pt = 0; p.pl = 0;
-  launch_conv(p, true, stream);
-  auto dx = at::empty({dy.size(0), H, W, wt.size(0)}, dy.options());
-  TORCH_CHECK(wt.size(0) % 8 == 0, "reflect dgrad: Cin % 8 != 0");
-  long total = dx.numel() / 8;
   int threads = 256;
+  if (stride == 1 && HP * WP > H * W && glds_eligible(p) &&
+      !env_flag(getenv("CYG_NO_DIRECT_FOLD"))) {
+    // image + ring are exactly the padded frame's size: dx is the leading
+    // [B,H,W,C] of the same allocation, the ring image the rest
+    auto dx = dxp.view({-1}).narrow(0, 0, nimg).view({B, H, W, C});
+    p.ringoff = nimg;
+    p.wt = pt; p.wl = pl; p.wH = H; p.wW = W;
+    launch_conv(p, true, stream);
+    const Span2 rs = mirror_span(H, pt, pb), cs = mirror_span(W, pl, pr);
+    const long nr = rs.n0 + rs.n1, nc = cs.n0 + cs.n1;
+    const long total = B * (nr * W + (H - nr) * nc) * (C / 8);
+    if (total > 0)
+      hipLaunchKernelGGL(reflect_ring_add_kernel, dim3(cdiv(total, threads)),
+                         dim3(threads), 0, stream, p.y, p.y + nimg, (int)B,
+                         (int)H, (int)W, (int)C, (int)pt, (int)pb, (int)pl,
+                         (int)pr, rs, cs);
+    return dx;
+  }
+  // full-frame fold: dgrad into the padded frame, then fold mirrors back
+  launch_conv(p, true, stream);
+  auto dx = at::empty({B, H, W, C}, dy.options());
+  long total = dx.numel() / 8;
   hipLaunchKernelGGL(reflect_fold_kernel, dim3(cdiv(total, threads)),
                      dim3(threads), 0, stream,
                      (const short*)dxp.const_data_ptr(),
