@@ -44,18 +44,34 @@ def resize_bilinear(img: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
     return y.squeeze(0).permute(1, 2, 0)
 
 
-def preprocess_train(img_u8: torch.Tensor, gen: torch.Generator,
-                     image_shape=(286, 286), crop=(256, 256)) -> torch.Tensor:
+def draw_train_params(gen: torch.Generator, src_hw, image_shape=(286, 286),
+                      crop=(256, 256)) -> Tuple[int, int, int]:
+    """One sample's augmentation draw -> (flip, oy, ox). The crop offsets
+    range over the RESIZED image (image_shape), so src_hw does not enter;
+    draw order is rand, randint(max_y+1), randint(max_x+1)."""
+    flip = int(torch.rand((), generator=gen).item() < 0.5)
+    max_y, max_x = image_shape[0] - crop[0], image_shape[1] - crop[1]
+    oy = int(torch.randint(0, max_y + 1, (), generator=gen))
+    ox = int(torch.randint(0, max_x + 1, (), generator=gen))
+    return flip, oy, ox
+
+
+def apply_train_aug(img_u8: torch.Tensor, flip: int, oy: int, ox: int,
+                    image_shape=(286, 286), crop=(256, 256)) -> torch.Tensor:
     img = img_u8.float()
-    if torch.rand((), generator=gen).item() < 0.5:
+    if flip:
         img = img.flip(1)  # left-right
     img = resize_bilinear(img, image_shape)
     ch, cw = crop
-    max_y, max_x = img.shape[0] - ch, img.shape[1] - cw
-    oy = int(torch.randint(0, max_y + 1, (), generator=gen))
-    ox = int(torch.randint(0, max_x + 1, (), generator=gen))
     img = img[oy:oy + ch, ox:ox + cw, :]
     return img / 127.5 - 1.0
+
+
+def preprocess_train(img_u8: torch.Tensor, gen: torch.Generator,
+                     image_shape=(286, 286), crop=(256, 256)) -> torch.Tensor:
+    flip, oy, ox = draw_train_params(gen, tuple(img_u8.shape[:2]),
+                                     image_shape, crop)
+    return apply_train_aug(img_u8, flip, oy, ox, image_shape, crop)
 
 
 def preprocess_test(img_u8: torch.Tensor, size=(256, 256)) -> torch.Tensor:
@@ -69,18 +85,42 @@ def synthetic_images(n: int, seed: int, hw: Tuple[int, int] = (256, 256)) -> Lis
                           dtype=torch.uint8) for _ in range(n)]
 
 
+def folder_image_names(path: str) -> List[str]:
+    return [name for name in sorted(os.listdir(path))
+            if name.lower().endswith((".jpg", ".jpeg", ".png"))]
+
+
 def folder_images(path: str) -> List[torch.Tensor]:
     import PIL.Image
     import numpy as np
     out = []
-    for name in sorted(os.listdir(path)):
-        if name.lower().endswith((".jpg", ".jpeg", ".png")):
-            with PIL.Image.open(os.path.join(path, name)) as im:
-                # np.asarray of a PIL image is read-only; copy so the
-                # tensor owns writable memory (torch warns otherwise)
-                out.append(torch.from_numpy(
-                    np.array(im.convert("RGB"), dtype="uint8")))
+    for name in folder_image_names(path):
+        with PIL.Image.open(os.path.join(path, name)) as im:
+            # np.asarray of a PIL image is read-only; copy so the
+            # tensor owns writable memory (torch warns otherwise)
+            out.append(torch.from_numpy(
+                np.array(im.convert("RGB"), dtype="uint8")))
     return out
+
+
+def load_raw(args, image_size: int, seed: int) -> dict:
+    """uint8 [H,W,3] images of the four splits: --data_dir folders, else the
+    deterministic synthetic clone."""
+    data_dir = getattr(args, "data_dir", None)
+    n_train = getattr(args, "num_train_samples", None)
+    n_test = getattr(args, "num_test_samples", None)
+    if data_dir:
+        return {s: folder_images(os.path.join(data_dir, s)) for s in SPLITS}
+    return {s: synthetic_images(
+        n if (n := {"trainA": n_train, "trainB": n_train,
+                    "testA": n_test, "testB": n_test}[s]) else SPLITS[s],
+        seed=seed + i, hw=(image_size, image_size))
+        for i, s in enumerate(SPLITS)}
+
+
+def resize_shape(image_size: int) -> Tuple[int, int]:
+    ih = (286 * image_size) // 256  # scale the 286/256 ratio with size
+    return (ih, ih)
 
 
 class ShuffleBuffer:
@@ -110,27 +150,16 @@ class Pipeline:
         self.per_replica = args.batch_size
         self.image_size = image_size
         self.seed = getattr(args, "seed", 1234)
-        data_dir = getattr(args, "data_dir", None)
-        n_train = getattr(args, "num_train_samples", None)
-        n_test = getattr(args, "num_test_samples", None)
 
         gen = torch.Generator().manual_seed(self.seed)
-        if data_dir:
-            raw = {s: folder_images(os.path.join(data_dir, s)) for s in SPLITS}
-        else:
-            raw = {s: synthetic_images(
-                n if (n := {"trainA": n_train, "trainB": n_train,
-                            "testA": n_test, "testB": n_test}[s]) else SPLITS[s],
-                seed=self.seed + i, hw=(image_size, image_size))
-                for i, s in enumerate(SPLITS)}
+        raw = load_raw(args, image_size, self.seed)
 
         self.num_train = min(len(raw["trainA"]), len(raw["trainB"]))
         self.num_test = min(len(raw["testA"]), len(raw["testB"]))
         self.train_steps = math.ceil(self.num_train / self.global_batch)
         self.test_steps = math.ceil(self.num_test / self.global_batch)
 
-        ih = (286 * image_size) // 256  # scale the 286/256 ratio with size
-        ishape, cshape = (ih, ih), (image_size, image_size)
+        ishape, cshape = resize_shape(image_size), (image_size, image_size)
         # .map().cache(): augmentation frozen per-sample for the run
         self.trainA = [preprocess_train(im, gen, ishape, cshape)
                        for im in raw["trainA"][: self.num_train]]

@@ -66,6 +66,8 @@ void adam_step_dev(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
 void shadow_gather(at::Tensor, at::Tensor, at::Tensor);
 void adam_step(at::Tensor, at::Tensor, at::Tensor, at::Tensor, double, double,
                double, double, int64_t);
+at::Tensor augment_batch(at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
+                         at::Tensor);
 }  // namespace cyg
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -113,4 +115,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step", &cyg::adam_step);
   m.def("adam_step_dev", &cyg::adam_step_dev);
   m.def("shadow_gather", &cyg::shadow_gather);
+  m.def("augment_batch", &cyg::augment_batch);
 }

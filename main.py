@@ -8,7 +8,10 @@ Multi-GPU (DP/RCCL): python -m torch.distributed.run --nnodes=1
                      --nproc-per-node 8 --master-addr 127.0.0.1 main.py ...
 
 Extra flags cover the BASELINE.json configs only (synthetic data source,
-image size, resblock count, dtype).
+image size, resblock count, dtype) and the input path: --data_device gpu
+keeps the dataset on the device as uint8 and builds every batch with one
+augmentation kernel (data/device.py); --augment epoch re-draws the
+augmentation each epoch (device path only).
 """
 
 from __future__ import annotations
@@ -24,7 +27,7 @@ from tqdm import tqdm
 
 from cyclegan_amd.parallel import DistContext
 from cyclegan_amd.trainer import CycleGAN
-from cyclegan_amd.data import Pipeline, DevicePrefetcher
+from cyclegan_amd.data import Pipeline, DevicePipeline, DevicePrefetcher
 from cyclegan_amd import utils
 
 
@@ -34,14 +37,25 @@ def train(args, pipe, gan, summary, epoch: int):
     # measures); short final batches and multi-rank training run eager
     use_graph = (gan.device.type == "cuda" and gan.ctx.world_size == 1
                  and not os.environ.get("CYG_NO_GRAPH"))
-    it = DevicePrefetcher(pipe.train_epoch(epoch), gan.device, gan.compute_dtype)
+    if args.data_device == "gpu":
+        # batches are born on the device in the compute dtype; once the
+        # graph exists they are written straight into its static inputs
+        static = ((gan.graphed.sx, gan.graphed.sy)
+                  if gan.graphed is not None else None)
+        it = pipe.train_epoch(epoch, out=static)
+    else:
+        it = DevicePrefetcher(pipe.train_epoch(epoch), gan.device,
+                              gan.compute_dtype)
     for x, y in tqdm(it, desc="Train", total=pipe.train_steps,
                      disable=args.verbose == 0 or not gan.ctx.is_main):
         if use_graph and x.shape[0] == args.batch_size:
             if gan.graphed is None:
                 from cyclegan_amd.trainer import GraphedStep
                 gan.graphed = GraphedStep(gan, x, y, preserve_state=True)
-            result = gan.graphed.call_cloned(x, y)
+            if x is gan.graphed.sx:  # already written in place: no copy
+                result = gan.graphed.call_cloned(None, None)
+            else:
+                result = gan.graphed.call_cloned(x, y)
         else:
             result = gan.train_step(x, y)
         utils.append_dict(results, result)
@@ -53,7 +67,9 @@ def train(args, pipe, gan, summary, epoch: int):
 
 def test(args, pipe, gan, summary, epoch: int):
     results = {}
-    it = DevicePrefetcher(pipe.test_epoch(), gan.device, gan.compute_dtype)
+    it = pipe.test_epoch()
+    if args.data_device != "gpu":
+        it = DevicePrefetcher(it, gan.device, gan.compute_dtype)
     for x, y in tqdm(it, desc="Test", total=pipe.test_steps,
                      disable=args.verbose == 0 or not gan.ctx.is_main):
         result = gan.test_step(x, y)
@@ -88,7 +104,11 @@ def main(args):
 
     summary = utils.Summary(args.output_dir) if ctx.is_main else None
 
-    pipe = Pipeline(args, ctx, image_size=args.image_size)
+    if args.data_device == "gpu":
+        pipe = DevicePipeline(args, ctx, image_size=args.image_size,
+                              augment=args.augment)
+    else:
+        pipe = Pipeline(args, ctx, image_size=args.image_size)
     args.train_steps, args.test_steps = pipe.train_steps, pipe.test_steps
 
     gan = CycleGAN(args, ctx)
@@ -127,9 +147,10 @@ def main(args):
 
     if summary is not None:
         summary.close()
+    return gan
 
 
-if __name__ == "__main__":
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser()
     parser.add_argument("--output_dir", default="runs")
     parser.add_argument("--epochs", default=200, type=int)
@@ -147,5 +168,24 @@ if __name__ == "__main__":
     parser.add_argument("--num_train_samples", default=None, type=int)
     parser.add_argument("--num_test_samples", default=None, type=int)
     parser.add_argument("--seed", default=1234, type=int)
+    parser.add_argument("--data_device", default="host", choices=["host", "gpu"],
+                        help="host: batches built on the host and copied; "
+                             "gpu: uint8 dataset resident on the device, "
+                             "batches built by the augmentation kernel")
+    parser.add_argument("--augment", default="frozen", choices=["frozen", "epoch"],
+                        help="frozen: one augmentation per sample for the run "
+                             "(the reference's .map().cache()); epoch: re-drawn "
+                             "every epoch (needs --data_device gpu)")
+    return parser
 
-    main(parser.parse_args())
+
+def parse_args(argv=None) -> argparse.Namespace:
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.augment == "epoch" and args.data_device != "gpu":
+        parser.error("--augment epoch requires --data_device gpu")
+    return args
+
+
+if __name__ == "__main__":
+    main(parse_args())
