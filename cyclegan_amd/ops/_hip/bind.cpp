@@ -22,6 +22,9 @@ at::Tensor convt2d_dgrad(at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
                          int64_t, int64_t);
 at::Tensor conv2d_wgrad(at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
                         int64_t, int64_t, bool);
+void conv2d_wgrad_into(at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
+                       int64_t, int64_t, bool, at::Tensor, bool, bool);
+void fold_packed_dw_into(at::Tensor, at::Tensor, bool);
 at::Tensor mfma_probe(at::Tensor, at::Tensor);
 at::Tensor mx_probe(at::Tensor, at::Tensor, int64_t, int64_t);
 at::Tensor mx_probe16(at::Tensor, at::Tensor, int64_t, int64_t);
@@ -51,9 +54,11 @@ std::vector<at::Tensor> instnorm_fwd_q8(at::Tensor, at::Tensor, at::Tensor,
 std::vector<at::Tensor> instnorm_bwd(at::Tensor, at::Tensor, at::Tensor,
                                      at::Tensor, at::Tensor,
                                      c10::optional<at::Tensor>, int64_t,
-                                     double, c10::optional<at::Tensor>);
+                                     double, c10::optional<at::Tensor>,
+                                     c10::optional<at::Tensor>,
+                                     c10::optional<at::Tensor>, bool);
 at::Tensor act_bwd(at::Tensor, at::Tensor, int64_t, double);
-at::Tensor channel_sum(at::Tensor);
+at::Tensor channel_sum(at::Tensor, c10::optional<at::Tensor>, bool);
 at::Tensor reflect_pad_fwd(at::Tensor, int64_t, int64_t, int64_t, int64_t);
 at::Tensor reflect_pad_bwd(at::Tensor, int64_t, int64_t, int64_t, int64_t);
 at::Tensor persample_loss_fwd(at::Tensor, at::Tensor, bool);
@@ -78,6 +83,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_dgrad", &cyg::conv2d_dgrad);
   m.def("convt2d_dgrad", &cyg::convt2d_dgrad);
   m.def("conv2d_wgrad", &cyg::conv2d_wgrad);
+  // the reduce writes the parameter's true OHWI gradient block `out`
+  // (cropped / channel-transposed / added to), e.g. a flat-grad view
+  m.def("conv2d_wgrad_into", &cyg::conv2d_wgrad_into, py::arg("x"),
+        py::arg("dy"), py::arg("kh"), py::arg("kw"), py::arg("stride"),
+        py::arg("pt"), py::arg("pl"), py::arg("reflect"), py::arg("out"),
+        py::arg("accumulate"), py::arg("transpose_oi") = false);
+  m.def("fold_packed_dw_into", &cyg::fold_packed_dw_into, py::arg("dwp"),
+        py::arg("out"), py::arg("accumulate"));
   m.def("mfma_probe", &cyg::mfma_probe);
   m.def("mx_probe", &cyg::mx_probe);
   m.def("mx_probe16", &cyg::mx_probe16);
@@ -103,9 +116,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("amax_cur"));
   m.def("instnorm_bwd", &cyg::instnorm_bwd, py::arg("dy"), py::arg("x"),
         py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("yact"),
-        py::arg("act"), py::arg("slope"), py::arg("beta") = py::none());
+        py::arg("act"), py::arg("slope"), py::arg("beta") = py::none(),
+        py::arg("dgamma_out") = py::none(), py::arg("dbeta_out") = py::none(),
+        py::arg("accumulate") = false);
   m.def("act_bwd", &cyg::act_bwd);
-  m.def("channel_sum", &cyg::channel_sum);
+  m.def("channel_sum", &cyg::channel_sum, py::arg("x"),
+        py::arg("out") = py::none(), py::arg("accumulate") = false);
   m.def("reflect_pad_fwd", &cyg::reflect_pad_fwd);
   m.def("reflect_pad_bwd", &cyg::reflect_pad_bwd);
   m.def("persample_loss_fwd", &cyg::persample_loss_fwd);

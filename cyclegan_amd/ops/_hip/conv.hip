@@ -1632,6 +1632,81 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws,
   dw[(long)n * KTOT + k] = (s0 + s1) + (s2 + s3);
 }
 
+// wgrad_reduce_kernel that finishes the gradient where the optimizer reads
+// it: out is the parameter's own OHWI block (typically a 4-byte-aligned
+// view into the flat grad buffer, hence scalar stores). The slab sum is the
+// same four chains as above; what differs is the store:
+//   crop     the GEMM ran on channel counts padded to 8 (cin_g, Cout);
+//            elements outside (co_true, ci_true) are skipped
+//   tr       transpose-conv gradient: the GEMM result is [Cin_w,KH,KW,Cout_w]
+//            and (n, tap, ci) goes to out[ci][tap][n]
+//   accum    out += sum (one more fp32 add, performed last) for a parameter
+//            that already received a gradient in this backward pass
+__global__ void wgrad_reduce_into_kernel(const float* __restrict__ ws,
+                                         float* __restrict__ out, long KTOT,
+                                         int Cout, int ktiles, int ntiles,
+                                         int slices, int wbn, int cin_g,
+                                         int taps, int co_true, int ci_true,
+                                         int tr, int accum) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long total = (long)ktiles * WG_BK * ntiles * wbn;
+  if (idx >= total) return;
+  int kl = (int)(idx % WG_BK);
+  long t = idx / WG_BK;
+  int kt = (int)(t % ktiles);
+  t /= ktiles;
+  int nl = (int)(t % wbn);
+  int nt = (int)(t / wbn);
+  long k = (long)kt * WG_BK + kl;
+  int n = nt * wbn + nl;
+  if (k >= KTOT || n >= Cout) return;
+  int tap = (int)(k / cin_g);
+  int ci = (int)(k - (long)tap * cin_g);
+  if (n >= co_true || ci >= ci_true) return;
+  long stride = (long)ktiles * ntiles * wbn * WG_BK;
+  long off = (((long)kt * ntiles + nt) * wbn + nl) * WG_BK + kl;
+  float s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+  int sl = 0;
+  for (; sl + 4 <= slices; sl += 4) {
+    s0 += ws[off + (sl + 0) * stride];
+    s1 += ws[off + (sl + 1) * stride];
+    s2 += ws[off + (sl + 2) * stride];
+    s3 += ws[off + (sl + 3) * stride];
+  }
+  for (; sl < slices; ++sl) s0 += ws[off + sl * stride];
+  float s = (s0 + s1) + (s2 + s3);
+  long o = tr ? ((long)ci * taps + tap) * co_true + n
+              : ((long)n * taps + tap) * ci_true + ci;
+  out[o] = accum ? out[o] + s : s;
+}
+
+// packed-head fold: the packed wgrad's [64, KH, 2, 8*I] result (n = d*8+co,
+// the 8 pixel shifts d folded into N) -> OHWI [O, KH, KW, I] with O <= 8,
+// KW <= 9. One thread per output element, its eight d terms summed in
+// ascending d: dw[co][ty][tx][ci] = Σ_d dwp[d*8+co][ty][blk][pos*I+ci],
+// blk*8+pos = tx+d.
+__global__ void fold_packed_dw_kernel(const float* __restrict__ dwp,
+                                      float* __restrict__ out, int O, int KH,
+                                      int KW, int I, int accum) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long total = (long)O * KH * KW * I;
+  if (idx >= total) return;
+  int ci = (int)(idx % I);
+  long t = idx / I;
+  int tx = (int)(t % KW);
+  t /= KW;
+  int ty = (int)(t % KH);
+  int co = (int)(t / KH);
+  float s = 0.f;
+  #pragma unroll
+  for (int d = 0; d < 8; ++d) {
+    int a = tx + d;  // < 16
+    s += dwp[((((long)(d * 8 + co) * KH + ty) * 2 + (a >> 3)) * 8 + (a & 7)) *
+                 I + ci];
+  }
+  out[idx] = accum ? out[idx] + s : s;
+}
+
 // ---------------- reflect fold (dgrad border scatter) ----------------
 // dx[b,i,j,c] = Σ over padded positions q with mirror(q - pad) == (i,j)
 // vectorized: one thread folds 8 channels of one (b,i,j); the candidate
@@ -2146,8 +2221,13 @@ static void launch_wgrad_glds(const WgradParams& p, dim3 grid,
                      stream, p);
 }
 
-at::Tensor conv2d_wgrad(at::Tensor x, at::Tensor dy, int64_t KH, int64_t KW,
-                        int64_t stride, int64_t pt, int64_t pl, bool reflect) {
+// into == nullptr: returns the GEMM-shaped [Cout,KH,KW,Cin] gradient.
+// Otherwise the reduce writes (or adds to) *into, cropped / transposed as
+// wgrad_reduce_into_kernel describes, and *into is returned.
+static at::Tensor wgrad_impl(at::Tensor x, at::Tensor dy, int64_t KH,
+                             int64_t KW, int64_t stride, int64_t pt,
+                             int64_t pl, bool reflect, const at::Tensor* into,
+                             bool accumulate, bool transpose_oi) {
   TORCH_CHECK(x.is_cuda() && dy.is_cuda() && x.is_contiguous() && dy.is_contiguous());
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 && dy.scalar_type() == at::kBFloat16);
   TORCH_CHECK(dy.size(0) == x.size(0));
@@ -2177,11 +2257,19 @@ at::Tensor conv2d_wgrad(at::Tensor x, at::Tensor dy, int64_t KH, int64_t KW,
                         x.options().dtype(at::kFloat));
     p.dw = (float*)dw.mutable_data_ptr();
     hipLaunchKernelGGL(wgrad_kernel, grid, dim3(NTHREADS), 0, stream, p);
-    return dw;
+    if (!into) return dw;
+    // no model shape comes here: finish with one ATen copy_/add_
+    auto v = transpose_oi ? dw.permute({3, 1, 2, 0}) : dw;
+    v = v.narrow(0, 0, into->size(0)).narrow(3, 0, into->size(3));
+    if (accumulate) into->add_(v); else into->copy_(v);
+    return *into;
   }
-  auto dw = at::empty({p.Cout, (long)KH, (long)KW, p.Cin},
-                      x.options().dtype(at::kFloat));
-  p.dw = (float*)dw.mutable_data_ptr();
+  at::Tensor dw;
+  if (!into) {
+    dw = at::empty({p.Cout, (long)KH, (long)KW, p.Cin},
+                   x.options().dtype(at::kFloat));
+    p.dw = (float*)dw.mutable_data_ptr();
+  }
   auto ws = at::empty({(long)p.slices * p.ktiles * p.ntiles * wbn * WG_BK},
                       x.options().dtype(at::kFloat));
   p.ws = (float*)ws.mutable_data_ptr();
@@ -2191,11 +2279,72 @@ at::Tensor conv2d_wgrad(at::Tensor x, at::Tensor dy, int64_t KH, int64_t KW,
     default: launch_wgrad_glds<64>(p, grid, stream);
   }
   long total = (long)p.ktiles * WG_BK * p.ntiles * wbn;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total, 256)),
+  if (!into) {
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total, 256)),
+                       dim3(256), 0, stream,
+                       (const float*)ws.const_data_ptr(), p.dw, p.KTOT,
+                       p.Cout, p.ktiles, p.ntiles, p.slices, wbn);
+    return dw;
+  }
+  const int co_true = (int)into->size(transpose_oi ? 3 : 0);
+  const int ci_true = (int)into->size(transpose_oi ? 0 : 3);
+  hipLaunchKernelGGL(wgrad_reduce_into_kernel, dim3(cdiv(total, 256)),
                      dim3(256), 0, stream,
-                     (const float*)ws.const_data_ptr(), p.dw, p.KTOT,
-                     p.Cout, p.ktiles, p.ntiles, p.slices, wbn);
-  return dw;
+                     (const float*)ws.const_data_ptr(),
+                     (float*)into->mutable_data_ptr(), p.KTOT, p.Cout,
+                     p.ktiles, p.ntiles, p.slices, wbn, p.Cin, (int)(KH * KW),
+                     co_true, ci_true, transpose_oi ? 1 : 0,
+                     accumulate ? 1 : 0);
+  return *into;
+}
+
+at::Tensor conv2d_wgrad(at::Tensor x, at::Tensor dy, int64_t KH, int64_t KW,
+                        int64_t stride, int64_t pt, int64_t pl, bool reflect) {
+  return wgrad_impl(x, dy, KH, KW, stride, pt, pl, reflect, nullptr, false,
+                    false);
+}
+
+static void check_grad_dest(const at::Tensor& out, const char* who) {
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat &&
+                  out.is_contiguous(),
+              who, ": out must be a contiguous fp32 device tensor");
+}
+
+// conv2d_wgrad whose reduce writes the parameter's true OHWI block `out`
+// (see wgrad_reduce_into_kernel). The GEMM channel counts may be the
+// padded ones; out.size(0)/out.size(3) are the true ones.
+void conv2d_wgrad_into(at::Tensor x, at::Tensor dy, int64_t KH, int64_t KW,
+                       int64_t stride, int64_t pt, int64_t pl, bool reflect,
+                       at::Tensor out, bool accumulate, bool transpose_oi) {
+  check_grad_dest(out, "conv2d_wgrad_into");
+  TORCH_CHECK(out.dim() == 4 && out.size(1) == KH && out.size(2) == KW,
+              "conv2d_wgrad_into: out must be [O,KH,KW,I]");
+  const int64_t co = out.size(transpose_oi ? 3 : 0);
+  const int64_t ci = out.size(transpose_oi ? 0 : 3);
+  TORCH_CHECK(co >= 1 && co <= dy.size(3) && ci >= 1 && ci <= x.size(3),
+              "conv2d_wgrad_into: out channels exceed the GEMM's");
+  wgrad_impl(x, dy, KH, KW, stride, pt, pl, reflect, &out, accumulate,
+             transpose_oi);
+}
+
+// packed-head fold (fold_packed_dw_kernel): dwp is conv2d_wgrad's result
+// for the 8-pixel-packed head, out the head weight's OHWI gradient block.
+void fold_packed_dw_into(at::Tensor dwp, at::Tensor out, bool accumulate) {
+  check_grad_dest(out, "fold_packed_dw_into");
+  TORCH_CHECK(dwp.is_cuda() && dwp.scalar_type() == at::kFloat &&
+              dwp.is_contiguous() && dwp.dim() == 4 && out.dim() == 4);
+  const int64_t O = out.size(0), KH = out.size(1), KW = out.size(2),
+                I = out.size(3);
+  TORCH_CHECK(O >= 1 && O <= 8 && KW >= 1 && KW <= 9 && dwp.size(0) == 64 &&
+                  dwp.size(1) == KH && dwp.size(2) == 2 &&
+                  dwp.size(3) == 8 * I,
+              "fold_packed_dw_into: shape mismatch");
+  long total = out.numel();
+  hipLaunchKernelGGL(fold_packed_dw_kernel, dim3(cdiv(total, 256)), dim3(256),
+                     0, at::cuda::getCurrentCUDAStream(),
+                     (const float*)dwp.const_data_ptr(),
+                     (float*)out.mutable_data_ptr(), (int)O, (int)KH, (int)KW,
+                     (int)I, accumulate ? 1 : 0);
 }
 
 // ---- fp8 host wrappers ----

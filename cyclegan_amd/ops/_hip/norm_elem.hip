@@ -261,13 +261,18 @@ __global__ __launch_bounds__(NT) void in_bwd_reduce_kernel(
     const float* __restrict__ beta, const float* __restrict__ mean,
     const float* __restrict__ rstd,
     float* __restrict__ p1, float* __restrict__ p2, int B, long HW, int C,
-    int S, int act, float slope, float* __restrict__ dgb) {
+    int S, int act, float slope, float* __restrict__ zbeta,
+    float* __restrict__ zgamma) {
   int b = blockIdx.x / S;
   int sl = blockIdx.x % S;
-  // zero the dgamma/dbeta accumulator the NEXT kernel (in_bwd_dx) fills
-  // with atomics — saves the host-side at::zeros fill launch
-  if (blockIdx.x == 0)
-    for (int i = threadIdx.x; i < 2 * C; i += NT) dgb[i] = 0.f;
+  // zero the dgamma/dbeta accumulators the NEXT kernel (in_bwd_dx) fills
+  // with atomics — saves the host-side at::zeros fill launch. Null when
+  // the caller accumulates onto what the destinations already hold.
+  if (blockIdx.x == 0 && zbeta != nullptr)
+    for (int i = threadIdx.x; i < C; i += NT) {
+      zbeta[i] = 0.f;
+      zgamma[i] = 0.f;
+    }
   long rows = (HW + S - 1) / S;
   long r0 = sl * rows, r1 = min(r0 + rows, HW);
   const int gpr = C / 8;
@@ -454,7 +459,7 @@ __global__ __launch_bounds__(NT) void in_bwd_dx_kernel(
 // ---- channel sum: out[c] = sum over (b,h,w) of x[...,c] (bias grads) ----
 __global__ __launch_bounds__(NT) void channel_sum_kernel(
     const short* __restrict__ x, float* __restrict__ out, long rows, int C,
-    int S) {
+    int S, int nout) {
   int sl = blockIdx.x;
   long per = (rows + S - 1) / S;
   long r0 = sl * per, r1 = min(r0 + per, rows);
@@ -473,7 +478,7 @@ __global__ __launch_bounds__(NT) void channel_sum_kernel(
   #pragma unroll
   for (int j = 0; j < 8; ++j) red[tid * 17 + j] = a[j];
   __syncthreads();
-  for (int c = tid; c < C; c += NT) {
+  for (int c = tid; c < nout; c += NT) {  // nout <= C: the unpadded count
     int g2 = c / 8, j = c % 8;
     float t = 0;
     for (int k = 0; k < rstep; ++k) t += red[(g2 + k * gpr) * 17 + j];
@@ -833,9 +838,24 @@ std::vector<at::Tensor> instnorm_bwd(at::Tensor dy, at::Tensor x,
                                      at::Tensor rstd,
                                      c10::optional<at::Tensor> yact,
                                      int64_t act, double slope,
-                                     c10::optional<at::Tensor> beta) {
+                                     c10::optional<at::Tensor> beta,
+                                     c10::optional<at::Tensor> dgamma_out,
+                                     c10::optional<at::Tensor> dbeta_out,
+                                     bool accumulate) {
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 &&
               dy.is_contiguous() && x.is_contiguous());
+  // destinations: two separate fp32 [C] blocks (slices of a flat grad
+  // buffer) the atomics of in_bwd_dx land in; with accumulate they are not
+  // zeroed first
+  TORCH_CHECK(dgamma_out.has_value() == dbeta_out.has_value(),
+              "instnorm_bwd: pass both destinations or neither");
+  TORCH_CHECK(!accumulate || dgamma_out.has_value(),
+              "instnorm_bwd: accumulate needs destinations");
+  if (dgamma_out.has_value())
+    for (const at::Tensor* t : {&*dgamma_out, &*dbeta_out})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat &&
+                      t->is_contiguous() && t->numel() == x.size(3),
+                  "instnorm_bwd: destinations must be contiguous fp32 [C]");
   // without yact the relu/lrelu mask is recomputed from x, which needs
   // beta; tanh needs the output value itself
   TORCH_CHECK(act == ACT_NONE || yact.has_value() ||
@@ -856,9 +876,17 @@ std::vector<at::Tensor> instnorm_bwd(at::Tensor dy, at::Tensor x,
   auto fopt = x.options().dtype(at::kFloat);
   int S = slices_for(HW, B);
   auto dx = at::empty_like(x);
-  auto dgb = at::empty({2, C}, fopt);
-  auto dbeta = dgb[0];
-  auto dgamma = dgb[1];
+  at::Tensor dbeta, dgamma;
+  if (dgamma_out.has_value()) {
+    dbeta = *dbeta_out;
+    dgamma = *dgamma_out;
+  } else {
+    auto dgb = at::empty({2, C}, fopt);
+    dbeta = dgb[0];
+    dgamma = dgb[1];
+  }
+  float* zb = accumulate ? nullptr : (float*)dbeta.mutable_data_ptr();
+  float* zg = accumulate ? nullptr : (float*)dgamma.mutable_data_ptr();
   const short* yp = yact.has_value()
                         ? (const short*)yact->const_data_ptr() : nullptr;
 
@@ -872,7 +900,7 @@ std::vector<at::Tensor> instnorm_bwd(at::Tensor dy, at::Tensor x,
                      (const float*)rstd.const_data_ptr(),
                      (float*)p1.mutable_data_ptr(),
                      (float*)p2.mutable_data_ptr(), B, HW, C, S, (int)act,
-                     (float)slope, (float*)dgb.mutable_data_ptr());
+                     (float)slope, zb, zg);
   LAUNCH_MM(in_bwd_dx_kernel, mm, dim3(B * S), stream,
                      (const short*)dy.const_data_ptr(),
                      (const short*)x.const_data_ptr(), yp,
@@ -888,20 +916,39 @@ std::vector<at::Tensor> instnorm_bwd(at::Tensor dy, at::Tensor x,
   return {dx, dgamma, dbeta};
 }
 
-at::Tensor channel_sum(at::Tensor x) {
+// out (optional): a contiguous fp32 destination of the first out.numel()
+// <= C channels (a bias's slice of a flat grad buffer; x may be channel-
+// padded); with accumulate the sums are added to what it holds. The zero
+// fill stays a memset: the kernel has no grid-wide ordering to hide it
+// behind, and an accumulating call skips it.
+at::Tensor channel_sum(at::Tensor x, c10::optional<at::Tensor> dest,
+                       bool accumulate) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous());
   int C = x.size(-1);
   long rows = x.numel() / C;
   TORCH_CHECK(C % 8 == 0 && (C / 8) <= NT && NT % (C / 8) == 0,
               "channel_sum: unsupported C ", C);
-  auto out = at::empty({C}, x.options().dtype(at::kFloat));
-  CHECK_HIP(hipMemsetAsync(out.mutable_data_ptr(), 0, C * sizeof(float),
-                           at::cuda::getCurrentCUDAStream()));
+  TORCH_CHECK(!accumulate || dest.has_value(),
+              "channel_sum: accumulate needs a destination");
+  at::Tensor out;
+  if (dest.has_value()) {
+    out = *dest;
+    TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat &&
+                    out.is_contiguous() && out.numel() >= 1 &&
+                    out.numel() <= C,
+                "channel_sum: out must be contiguous fp32 of <= C elements");
+  } else {
+    out = at::empty({C}, x.options().dtype(at::kFloat));
+  }
+  const int nout = (int)out.numel();
+  if (!accumulate)
+    CHECK_HIP(hipMemsetAsync(out.mutable_data_ptr(), 0, nout * sizeof(float),
+                             at::cuda::getCurrentCUDAStream()));
   int S = (int)std::min<long>(512, std::max<long>(1, rows / 64));
   hipLaunchKernelGGL(channel_sum_kernel, dim3(S), dim3(NT), 0,
                      at::cuda::getCurrentCUDAStream(),
                      (const short*)x.const_data_ptr(),
-                     (float*)out.mutable_data_ptr(), rows, C, S);
+                     (float*)out.mutable_data_ptr(), rows, C, S, nout);
   return out;
 }
 

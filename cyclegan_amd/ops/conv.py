@@ -33,7 +33,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 import torch.nn.functional as F
 
-from . import backend
+from . import backend, grad_sink
 from .shadow import (compute_weight, compute_weight_t, compute_weight_p,
                      compute_weight_tp, compute_bias_p, compute_weight_packp,
                      compute_bias_packb, fp8_weight_shadow)
@@ -150,7 +150,7 @@ class _ConvFn(torch.autograd.Function):
             y = ext.conv2d_fwd(xp, wc, bc, stride, *pads, reflect, act, slope)
         if cout < 8:
             y = y[..., :cout].contiguous()
-        ctx.save_for_backward(xp, w, y)
+        ctx.save_for_backward(xp, w, y, bias)
         ctx.conf = (stride, pads, reflect, act, slope, bias is not None,
                     x.shape[3])
         if slabs:
@@ -164,18 +164,19 @@ class _ConvFn(torch.autograd.Function):
     def backward(ctx, dy, *_):
         if dy is None:  # only with set_materialize_grads(False): y unused
             return (None,) * 8
-        xp, w, y = ctx.saved_tensors
+        xp, w, y, bias = ctx.saved_tensors
         stride, pads, reflect, act, slope, has_bias, cin = ctx.conf
         cout = w.shape[0]
         pt, pb, pl, pr = pads
         ext = backend.ext()
+        sink = grad_sink.current()
         dy = dy.contiguous()
         if act != ACT_NONE:
             dy = ext.act_bwd(dy, y, act, slope)
         dyp = _pad_channels(dy).contiguous()
         db = None
         if has_bias and ctx.needs_input_grad[2]:
-            db = ext.channel_sum(dyp)[: dy.shape[-1]]
+            db = _bias_grad(ext, sink, bias, dyp, dy.shape[-1])
         dx = dw = None
         if ctx.needs_input_grad[0]:
             wt = compute_weight_tp(w, xp)
@@ -183,14 +184,30 @@ class _ConvFn(torch.autograd.Function):
                                   pt, pb, pl, pr, reflect)
             if cin < 8:
                 dx = dx[..., :cin].contiguous()
-        if ctx.needs_input_grad[1]:
-            dw = ext.conv2d_wgrad(xp, dyp, w.shape[1], w.shape[2], stride,
-                                  pt, pl, reflect)
-            if cout < 8 or cin < 8:
-                dw = dw[:cout, :, :, :cin].contiguous()
-            if dw.dtype != w.dtype:
-                dw = dw.to(w.dtype)
+        if ctx.needs_input_grad[1] and not grad_sink.frozen(sink, w):
+            if sink is not None and sink.has(w):
+                out, acc = sink.take(w)
+                ext.conv2d_wgrad_into(xp, dyp, w.shape[1], w.shape[2], stride,
+                                      pt, pl, reflect, out, acc, False)
+            else:
+                dw = ext.conv2d_wgrad(xp, dyp, w.shape[1], w.shape[2], stride,
+                                      pt, pl, reflect)
+                if cout < 8 or cin < 8:
+                    dw = dw[:cout, :, :, :cin].contiguous()
         return dx, dw, db, None, None, None, None, None
+
+
+def _bias_grad(ext, sink, bias, dyp, n):
+    """Bias gradient (channel sum of the padded dy, first n channels): into
+    the active sink's view, skipped for a frozen model's bias, returned to
+    autograd when no sink is active."""
+    if grad_sink.frozen(sink, bias):
+        return None
+    if sink is not None and sink.has(bias):
+        out, acc = sink.take(bias)
+        ext.channel_sum(dyp, out, acc)
+        return None
+    return ext.channel_sum(dyp)[:n]
 
 
 def _head_packable(x, w, stride, pads, reflect) -> bool:
@@ -239,34 +256,37 @@ class _ConvHeadPackedFn(torch.autograd.Function):
         y = yp.view(B, H, W, 8)
         if cout < 8:
             y = y[..., :cout].contiguous()
-        ctx.save_for_backward(xp, w, y)
+        ctx.save_for_backward(xp, w, y, bias)
         ctx.conf = (act, slope, bias is not None, cout, Cin, H, W)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        xp, w, y = ctx.saved_tensors
+        xp, w, y, bias = ctx.saved_tensors
         act, slope, has_bias, cout, Cin, H, W = ctx.conf
         ext = backend.ext()
+        sink = grad_sink.current()
         dy = dy.contiguous()
         if act != ACT_NONE:
             dy = ext.act_bwd(dy, y, act, slope)
         dyp = _pad_channels(dy).contiguous()
         db = None
         if has_bias and ctx.needs_input_grad[2]:
-            db = ext.channel_sum(dyp)[: dy.shape[-1]]
+            db = _bias_grad(ext, sink, bias, dyp, dy.shape[-1])
         dx = dw = None
         B = dyp.shape[0]
         if ctx.needs_input_grad[0]:
             wt = compute_weight_tp(w, xp)
             dx = ext.conv2d_dgrad(dyp, wt, H, W, 1, 3, 3, 3, 3, True)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and not grad_sink.frozen(sink, w):
             xf = xp.view(B, H + 6, (W + 8) // 8, 8 * Cin)
             dy_pk = dyp.view(B, H, W // 8, 64)
             dwp = ext.conv2d_wgrad(xf, dy_pk, 7, 2, 1, 0, 0, False)
-            dw = _fold_packed_dw(dwp, tuple(w.shape))
-            if dw.dtype != w.dtype:
-                dw = dw.to(w.dtype)
+            if sink is not None and sink.has(w):
+                out, acc = sink.take(w)
+                ext.fold_packed_dw_into(dwp, out, acc)
+            else:
+                dw = _fold_packed_dw(dwp, tuple(w.shape))
         return dx, dw, db, None, None
 
 
@@ -386,7 +406,7 @@ class _ConvFp8Fn(torch.autograd.Function):
                                    reflect, act, slope)
         if cout < 8:
             y = y[..., :cout].contiguous()
-        ctx.save_for_backward(xp, w, y)
+        ctx.save_for_backward(xp, w, y, bias)
         ctx.conf = (stride, pads, reflect, act, slope, bias is not None,
                     x.shape[3])
         if slabs:
@@ -432,6 +452,7 @@ class _ConvTFn(torch.autograd.Function):
         x, w, y = ctx.saved_tensors
         stride, pt, pl, act, slope, has_bias = ctx.conf
         ext = backend.ext()
+        sink = grad_sink.current()
         dy = dy.contiguous()
         if act != ACT_NONE:
             dy = ext.act_bwd(dy, y, act, slope)
@@ -440,14 +461,18 @@ class _ConvTFn(torch.autograd.Function):
             # adjoint of the gather is the forward strided conv of dy
             wt = compute_weight_t(w, x)
             dx = ext.convt2d_dgrad(dy, wt, x.shape[1], x.shape[2], stride, pt, pl)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and not grad_sink.frozen(sink, w):
             # convT wgrad == conv wgrad with roles swapped (x := dy, dy := x),
-            # then a channel transpose back to OHWI
-            dwc = ext.conv2d_wgrad(dy, x, w.shape[1], w.shape[2], stride,
-                                   pt, pl, False)
-            dw = dwc.permute(3, 1, 2, 0).contiguous()
-            if dw.dtype != w.dtype:
-                dw = dw.to(w.dtype)
+            # then a channel transpose back to OHWI (done by the reduce's
+            # store when it writes into the sink)
+            if sink is not None and sink.has(w):
+                out, acc = sink.take(w)
+                ext.conv2d_wgrad_into(dy, x, w.shape[1], w.shape[2], stride,
+                                      pt, pl, False, out, acc, True)
+            else:
+                dwc = ext.conv2d_wgrad(dy, x, w.shape[1], w.shape[2], stride,
+                                       pt, pl, False)
+                dw = dwc.permute(3, 1, 2, 0).contiguous()
         if has_bias and ctx.needs_input_grad[2]:
             db = dy.float().sum(dim=(0, 1, 2))
         return dx, dw, db, None, None, None, None, None, None, None

@@ -19,7 +19,7 @@ from typing import Optional
 
 import torch
 
-from . import backend
+from . import backend, grad_sink
 from . import conv as _conv
 from .conv import (ACT_NONE, ACT_RELU, ACT_LRELU, FP8_TWIN_ATTR,
                    IN_SLABS_ATTR, _ACT, Fp8Consumer)
@@ -94,18 +94,32 @@ class _InstNormFn(torch.autograd.Function):
         eps, act, slope, has_res = ctx.conf
         ext = backend.ext()
         dy = dy.contiguous()
+        # both parameters in the active sink: in_bwd_dx's atomics land in
+        # their flat-grad views. Otherwise (no sink, or a model frozen for
+        # this pass) the kernels run as ever into a buffer of their own.
+        sink = grad_sink.current()
+        dest = (None, None, False)
+        if sink is not None and sink.has(gamma) and sink.has(betaf):
+            dg_out, acc = sink.take(gamma)
+            db_out, acc_b = sink.take(betaf)
+            assert acc == acc_b
+            dest = (dg_out, db_out, acc)
         if has_res and act != ACT_NONE:
             # rare combo: residual grad needs the transformed dy explicitly
             dy = ext.act_bwd(dy, y, act, slope)
             dres = dy
             dx, dgamma, dbeta = ext.instnorm_bwd(dy, x, gamma.float(), mean,
-                                                 rstd, None, ACT_NONE, 0.0)
+                                                 rstd, None, ACT_NONE, 0.0,
+                                                 None, *dest)
         else:
             dres = dy if has_res else None
             yact = y if (act != ACT_NONE and not _mask_from_x(act)) else None
             dx, dgamma, dbeta = ext.instnorm_bwd(
-                dy, x, gamma.float(), mean, rstd, yact, act, slope, betaf)
-        return (dx, dgamma.to(gamma.dtype), dbeta, None, None, None, dres,
+                dy, x, gamma.float(), mean, rstd, yact, act, slope, betaf,
+                *dest)
+        if dest[0] is not None:
+            dgamma = dbeta = None
+        return (dx, dgamma, dbeta, None, None, None, dres,
                 None, None, None, None)
 
 

@@ -53,15 +53,37 @@ class FlatParamGroup:
         for p in self.params:
             torch.autograd.graph.increment_version(p)
 
-    def set_grads(self, grads):
+    def grad_sink(self):
+        """A fresh gradient sink over this group's flat-grad views
+        (ops.grad_sink), or None where the HIP backward functions that
+        fill it do not run (CPU) or CYG_NO_GRAD_SINK=1."""
+        from ..ops import grad_sink
+        if not (self.flat_grad.is_cuda and grad_sink.enabled()):
+            return None
+        return grad_sink.GradSink(self.params, [p.grad for p in self.params])
+
+    def set_grads(self, grads, sink=None):
         """Write a ``torch.autograd.grad`` result into the flat buffer.
 
-        One multi-tensor-apply copy per group instead of per-param
-        AccumulateGrad adds; every view is fully overwritten, so no
-        zero-fill between steps is needed."""
-        torch._foreach_copy_(
-            [p.grad for p in self.params],
-            [g.reshape(p.shape) for p, g in zip(self.params, grads)])
+        A gradient the backward pass already wrote through ``sink`` comes
+        back as None; the rest go in with one multi-tensor-apply copy per
+        group instead of per-param AccumulateGrad adds. Every view is
+        fully overwritten one way or the other, so no zero-fill between
+        steps is needed."""
+        dst, src = [], []
+        for p, g in zip(self.params, grads):
+            if g is None:
+                assert sink is not None and sink.touched(p), \
+                    "a parameter received no gradient"
+            elif sink is not None and sink.touched(p):
+                # one use wrote through the sink, another came back from
+                # autograd (no model does this today): keep both
+                p.grad.add_(g.reshape(p.shape))
+            else:
+                dst.append(p.grad)
+                src.append(g.reshape(p.shape))
+        if dst:
+            torch._foreach_copy_(dst, src)
 
     def zero_grad(self):
         self.flat_grad.zero_()

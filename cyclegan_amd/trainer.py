@@ -31,7 +31,7 @@ from typing import Dict, Optional
 import torch
 
 from .models import Generator, Discriminator
-from .ops import MAE, MSE, MSE_const, backend
+from .ops import MAE, MSE, MSE_const, backend, grad_sink
 from .ops.adam import FusedAdam
 from .parallel import DistContext, GradSync, FlatParamGroup
 
@@ -205,17 +205,25 @@ class CycleGAN:
                    retain: bool):
         """One group's backward pass into its flat grad buffer.
 
-        torch.autograd.grad (not .backward): grads come back as fresh
-        tensors and land in the flat buffer via ONE batched multi-tensor
-        copy per group, skipping AccumulateGrad's per-param add into the
-        .grad views (~300 tiny launches/step) and the flat zero-fill.
+        torch.autograd.grad (not .backward): no AccumulateGrad per-param
+        add into the .grad views (~300 tiny launches/step) and no flat
+        zero-fill. On the HIP path the backward kernels write each
+        gradient into its flat-grad view themselves (ops.grad_sink);
+        whatever autograd still returns as a tensor (CPU path,
+        CYG_NO_GRAD_SINK=1) lands there via ONE batched multi-tensor copy.
         retain_graph through X's pass: the shared discriminate_fake_*
         subgraphs are traversed by both the generator and discriminator
         passes."""
         key = dict(self._GROUP_LOSS)[name]
-        self.groups[name].set_grads(
-            torch.autograd.grad(losses[key], self.groups[name].params,
-                                retain_graph=retain))
+        group = self.groups[name]
+        # on the HIP path the kernels that finish a gradient write it into
+        # the flat buffer themselves (ops.grad_sink) and autograd gets None
+        sink = group.grad_sink()
+        with grad_sink.active(sink):
+            grads = torch.autograd.grad(losses[key], group.params,
+                                        retain_graph=retain,
+                                        allow_unused=sink is not None)
+        group.set_grads(grads, sink)
 
     def _optimize(self):
         for opt in self.optimizers.values():
