@@ -9,6 +9,9 @@ to explicit MI355X ops:
 - K9-K12 activations/add      -> fused epilogues in conv/norm
 - K13    loss elementwise     -> ops.losses.MAE/MSE/MSE_const
 - K14    Adam                 -> ops.adam.FusedAdam
+
+Beyond the reference: ops.augment (K15 input augmentation) and ops.pool
+(the CycleGAN image history pool).
 """
 
 from . import backend  # noqa: F401
@@ -17,3 +20,4 @@ from .conv import (conv2d, conv_transpose2d, same_pads, set_fp8_mode,  # noqa: F
 from .norm import instance_norm  # noqa: F401
 from .pad import reflection_pad2d  # noqa: F401
 from .losses import MAE, MSE, MSE_const, BCE  # noqa: F401
+from .pool import pool_exchange, ImagePool  # noqa: F401

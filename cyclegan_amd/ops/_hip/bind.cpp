@@ -73,6 +73,7 @@ void adam_step(at::Tensor, at::Tensor, at::Tensor, at::Tensor, double, double,
                double, double, int64_t);
 at::Tensor augment_batch(at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
                          at::Tensor);
+at::Tensor pool_exchange(at::Tensor, at::Tensor, at::Tensor, at::Tensor);
 }  // namespace cyg
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -132,4 +133,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step_dev", &cyg::adam_step_dev);
   m.def("shadow_gather", &cyg::shadow_gather);
   m.def("augment_batch", &cyg::augment_batch);
+  m.def("pool_exchange", &cyg::pool_exchange);
 }

@@ -20,7 +20,10 @@ on the MI355X execution model:
   reference's recomputed X(fake_x)/Y(fake_y) calls (main.py:239-245)
   under its var_list restriction, asserted by
   tests/test_trainer.py::test_train_step_grads_match_reference_structure;
-- compute dtype bf16 on GPU (fp32 masters), fp32 on CPU.
+- compute dtype bf16 on GPU (fp32 masters), fp32 on CPU;
+- optional image history pool (``pool_size`` > 0, ops/pool.py; not in the
+  reference): the discriminator losses see fakes exchanged with a buffer
+  of earlier ones, the generator losses keep the fresh fakes.
 """
 
 from __future__ import annotations
@@ -31,7 +34,7 @@ from typing import Dict, Optional
 import torch
 
 from .models import Generator, Discriminator
-from .ops import MAE, MSE, MSE_const, backend, grad_sink
+from .ops import MAE, MSE, MSE_const, ImagePool, backend, grad_sink
 from .ops.adam import FusedAdam
 from .parallel import DistContext, GradSync, FlatParamGroup
 
@@ -87,12 +90,72 @@ class CycleGAN:
                 _shadow.register_arena(a)
                 self.arenas[name] = a
 
+        # image history pools (fake x, fake y): built at the first step,
+        # when the image shape is known; every rank keeps its own
+        self.pool_size = int(getattr(args, "pool_size", 0) or 0)
+        self._pool_seed = (int(getattr(args, "seed", 1234)), int(ctx.rank))
+        self.pools = None
+        # int32 [b] device codes of the step being built (one per pool)
+        self._step_codes = None
+        # while a graph step warms up and captures: its static all-pass
+        # codes, so train_step draws nothing
+        self._static_codes = None
+
         # lazily-captured hip-graph step (main.py at N=1)
         self.graphed = None
 
     def _refresh_shadows(self):
         for a in self.arenas.values():
             a.refresh()
+
+    # ---- image history pool ----
+
+    def _ensure_pools(self, image_shape):
+        if self.pools is None:
+            self.pools = tuple(
+                ImagePool(self.pool_size, tuple(image_shape),
+                          self.compute_dtype, self.device,
+                          seed=self._pool_seed + (which,))
+                for which in (0, 1))
+        return self.pools
+
+    def plan_pools(self, batch_sizes, image_shape):
+        """Draw the pool decisions of the next ``len(batch_sizes)`` steps
+        now and keep them on the device: the steps then take one table row
+        each (ImagePool.next_codes) instead of an upload."""
+        for pool in self._ensure_pools(image_shape):
+            pool.plan(batch_sizes)
+
+    def static_pool_codes(self, x):
+        """All-pass codes for a graph step's warm-up and capture (None with
+        the pool off): they leave pool contents, fill counts and decision
+        streams alone. Set before each replay by refresh_pool_codes."""
+        if not self.pool_size:
+            return None
+        self._ensure_pools(x.shape[1:])  # allocated outside the capture
+        return tuple(torch.full((x.shape[0],), -1, dtype=torch.int32,
+                                device=self.device) for _ in self.pools)
+
+    def refresh_pool_codes(self, static_codes):
+        """Next step's decisions into a captured step's static codes: a
+        device-to-device row copy when the steps were planned."""
+        for pool, codes in zip(self.pools, static_codes):
+            codes.copy_(pool.next_codes(codes.shape[0]), non_blocking=True)
+
+    def _pooled_discriminator_losses(self, x, y, fake_x, fake_y):
+        """Discriminator losses on pooled fakes: one 2b-batched call per
+        discriminator. The pooled images carry no graph, so these losses
+        share nothing with the generator losses."""
+        b = x.shape[0]
+        out = []
+        for D, real, fake, pool, codes in (
+                (self.X, x, fake_x, self.pools[0], self._step_codes[0]),
+                (self.Y, y, fake_y, self.pools[1], self._step_codes[1])):
+            # (the HIP convs return contiguous NHWC: no copy there)
+            pooled = pool.exchange(fake.detach().contiguous(), codes)
+            d_real, d_fake = D(torch.cat([real, pooled])).split(b)
+            out.append(self.discriminator_loss(d_real, d_fake))
+        return out
 
     # ---- loss functions (reference main.py:172-195) ----
 
@@ -185,18 +248,25 @@ class CycleGAN:
         F_cycle_loss = self.cycle_loss(x, cycle_x)
         G_identity_loss = self.identity_loss(y, same_y)
         F_identity_loss = self.identity_loss(x, same_x)
-        return {
+        losses = {
             "loss_G/loss": G_loss, "loss_G/cycle": G_cycle_loss,
             "loss_G/identity": G_identity_loss,
             "loss_G/total": G_loss + G_cycle_loss + G_identity_loss,
             "loss_F/loss": F_loss, "loss_F/cycle": F_cycle_loss,
             "loss_F/identity": F_identity_loss,
             "loss_F/total": F_loss + F_cycle_loss + F_identity_loss,
-            "loss_X/loss": self.discriminator_loss(self.X(x),
-                                                   discriminate_fake_x),
-            "loss_Y/loss": self.discriminator_loss(self.Y(y),
-                                                   discriminate_fake_y),
         }
+        if self.pool_size:
+            # history pool: the discriminators train on exchanged fakes,
+            # so their pass over the fake is no longer the generators' one
+            losses["loss_X/loss"], losses["loss_Y/loss"] = \
+                self._pooled_discriminator_losses(x, y, fake_x, fake_y)
+        else:
+            losses["loss_X/loss"] = self.discriminator_loss(
+                self.X(x), discriminate_fake_x)
+            losses["loss_Y/loss"] = self.discriminator_loss(
+                self.Y(y), discriminate_fake_y)
+        return losses
 
     _GROUP_LOSS = (("G", "loss_G/total"), ("F", "loss_F/total"),
                    ("X", "loss_X/loss"), ("Y", "loss_Y/loss"))
@@ -213,7 +283,7 @@ class CycleGAN:
         CYG_NO_GRAD_SINK=1) lands there via ONE batched multi-tensor copy.
         retain_graph through X's pass: the shared discriminate_fake_*
         subgraphs are traversed by both the generator and discriminator
-        passes."""
+        passes (see _retain)."""
         key = dict(self._GROUP_LOSS)[name]
         group = self.groups[name]
         # on the HIP path the kernels that finish a gradient write it into
@@ -224,6 +294,13 @@ class CycleGAN:
                                         retain_graph=retain,
                                         allow_unused=sink is not None)
         group.set_grads(grads, sink)
+
+    def _retain(self, i: int) -> bool:
+        """retain_graph for the i-th pass of _GROUP_LOSS. Pool off: the
+        discriminate_fake_* subgraphs are shared, keep them until Y's pass.
+        Pool on: the four losses have disjoint graphs (cycle inputs and
+        pooled fakes are detached), each pass may free its own."""
+        return i < 3 and not self.pool_size
 
     def _optimize(self):
         for opt in self.optimizers.values():
@@ -239,9 +316,15 @@ class CycleGAN:
         x, y = self._cast(x), self._cast(y)
         if x.shape[0] == 0:
             return self._empty_train_step()
+        if self.pool_size:
+            # the eager step draws for itself; a graph step that is
+            # warming up or capturing has set its static codes instead
+            self._step_codes = self._static_codes or tuple(
+                pool.next_codes(x.shape[0])
+                for pool in self._ensure_pools(x.shape[1:]))
         losses = self._forward_losses(x, y)
         for i, (name, _) in enumerate(self._GROUP_LOSS):
-            self._grads_for(losses, name, retain=i < 3)
+            self._grads_for(losses, name, retain=self._retain(i))
             self.sync.launch(self.groups[name].flat_grad)
         self.sync.wait_all()
         self._optimize()
@@ -315,6 +398,9 @@ class CycleGAN:
                 "X_optimizer": self.optimizers["X"].state_dict(),
                 "Y_optimizer": self.optimizers["Y"].state_dict(),
             }
+            if self.pools is not None:  # this rank's; ranks are not synced
+                state["pool_x"] = self.pools[0].state_dict()
+                state["pool_y"] = self.pools[1].state_dict()
             tmp = self.checkpoint_path + ".tmp"
             torch.save(state, tmp)
             os.replace(tmp, self.checkpoint_path)
@@ -332,6 +418,12 @@ class CycleGAN:
         self.Y.load_state_dict(state["Y"])
         for name in ("G", "F", "X", "Y"):
             self.optimizers[name].load_state_dict(state[f"{name}_optimizer"])
+        if self.pool_size and "pool_x" in state:
+            # a checkpoint without pools starts them empty; with the pool
+            # off, saved pools are ignored
+            pools = self._ensure_pools(state["pool_x"]["buf"].shape[1:])
+            pools[0].load_state_dict(state["pool_x"])
+            pools[1].load_state_dict(state["pool_y"])
         self._refresh_shadows()
         print(f"\nloaded checkpoint from {self.checkpoint_path}\n")
         return True
@@ -377,6 +469,8 @@ class GraphedStep:
         self.gan = gan
         self.sx = gan._cast(x).clone()
         self.sy = gan._cast(y).clone()
+        # history pool: static codes, all-pass through warm-up and capture
+        self.codes = gan._static_codes = gan.static_pool_codes(self.sx)
         # preserve_state: roll model/optimizer state back after the warmup
         # steps so capturing mid-training perturbs nothing (main.py uses
         # this to capture on the first batch of an epoch)
@@ -385,6 +479,7 @@ class GraphedStep:
             saved = {n: (g.flat_param.clone(), gan.optimizers[n].m.clone(),
                          gan.optimizers[n].v.clone(), gan.optimizers[n].t)
                      for n, g in gan.groups.items()}
+            saved_pools = [p.state_dict() for p in gan.pools or ()]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -400,6 +495,7 @@ class GraphedStep:
         with torch.cuda.graph(self.graph):
             self.out = gan.train_step(self.sx, self.sy)
             self._packed = torch.stack([self.out[k] for k in self.gan._TRAIN_KEYS])
+        gan._static_codes = None  # eager steps draw for themselves again
         if saved is not None:
             with torch.no_grad():
                 for n, (p, m, v, t) in saved.items():
@@ -407,6 +503,8 @@ class GraphedStep:
                     gan.optimizers[n].m.copy_(m)
                     gan.optimizers[n].v.copy_(v)
                     gan.optimizers[n].t = t
+                for p, state in zip(gan.pools or (), saved_pools):
+                    p.load_state_dict(state)
                 gan._refresh_shadows()
 
     def __call__(self, x=None, y=None) -> Dict[str, torch.Tensor]:
@@ -415,6 +513,8 @@ class GraphedStep:
             self.sy.copy_(self.gan._cast(y))
         for opt in self.gan.optimizers.values():
             opt.advance_lr()
+        if self.codes is not None:
+            self.gan.refresh_pool_codes(self.codes)
         self.graph.replay()
         for g in self.gan.groups.values():
             g.bump_versions()
@@ -445,11 +545,14 @@ class SegmentedGraphedStep:
         self.gan = gan
         self.sx = gan._cast(x).clone()
         self.sy = gan._cast(y).clone()
+        # history pool: static codes, all-pass through warm-up and capture
+        self.codes = gan._static_codes = gan.static_pool_codes(self.sx)
         saved = None
         if preserve_state:
             saved = {n: (g.flat_param.clone(), gan.optimizers[n].m.clone(),
                          gan.optimizers[n].v.clone(), gan.optimizers[n].t)
                      for n, g in gan.groups.items()}
+            saved_pools = [p.state_dict() for p in gan.pools or ()]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -461,16 +564,17 @@ class SegmentedGraphedStep:
 
         self.names = [n for n, _ in gan._GROUP_LOSS]
         self.graphs = []
+        gan._step_codes = self.codes  # train_step's part, skipped below
         g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g1):
             losses = gan._forward_losses(self.sx, self.sy)
-            gan._grads_for(losses, "G", retain=True)
+            gan._grads_for(losses, "G", retain=gan._retain(0))
         self.graphs.append(g1)
         pool = g1.pool()
         for i, name in enumerate(self.names[1:], start=1):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool):
-                gan._grads_for(losses, name, retain=i < 3)
+                gan._grads_for(losses, name, retain=gan._retain(i))
             self.graphs.append(g)
         gopt = torch.cuda.CUDAGraph()
         with torch.cuda.graph(gopt, pool=pool):
@@ -484,6 +588,7 @@ class SegmentedGraphedStep:
         self.graphs.append(gopt)
         self.out = {k: losses[k].detach() for k in gan._TRAIN_KEYS}
 
+        gan._static_codes = None  # eager steps draw for themselves again
         if saved is not None:
             with torch.no_grad():
                 for n, (p, m, v, t) in saved.items():
@@ -491,6 +596,8 @@ class SegmentedGraphedStep:
                     gan.optimizers[n].m.copy_(m)
                     gan.optimizers[n].v.copy_(v)
                     gan.optimizers[n].t = t
+                for p, state in zip(gan.pools or (), saved_pools):
+                    p.load_state_dict(state)
                 gan._refresh_shadows()
 
     def __call__(self, x=None, y=None) -> Dict[str, torch.Tensor]:
@@ -500,6 +607,8 @@ class SegmentedGraphedStep:
             self.sy.copy_(gan._cast(y))
         for opt in gan.optimizers.values():
             opt.advance_lr()
+        if self.codes is not None:
+            gan.refresh_pool_codes(self.codes)
         for i, name in enumerate(self.names):
             self.graphs[i].replay()
             gan.sync.launch(gan.groups[name].flat_grad)

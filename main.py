@@ -11,7 +11,9 @@ Extra flags cover the BASELINE.json configs only (synthetic data source,
 image size, resblock count, dtype) and the input path: --data_device gpu
 keeps the dataset on the device as uint8 and builds every batch with one
 augmentation kernel (data/device.py); --augment epoch re-draws the
-augmentation each epoch (device path only).
+augmentation each epoch (device path only). --pool_size N updates the
+discriminators on a history of N generated images (the CycleGAN paper's
+image pool, N = 50 there; ops/pool.py).
 """
 
 from __future__ import annotations
@@ -46,6 +48,12 @@ def train(args, pipe, gan, summary, epoch: int):
     else:
         it = DevicePrefetcher(pipe.train_epoch(epoch), gan.device,
                               gan.compute_dtype)
+    if use_graph and gan.pool_size:
+        # the captured step cannot draw: plan the epoch's pool decisions
+        # now, one device table, and let every step take its row
+        gb, n = pipe.global_batch, pipe.num_train
+        sizes = [min(gb, n - s * gb) for s in range(pipe.train_steps)]
+        gan.plan_pools(sizes, (pipe.image_size, pipe.image_size, 3))
     for x, y in tqdm(it, desc="Train", total=pipe.train_steps,
                      disable=args.verbose == 0 or not gan.ctx.is_main):
         if use_graph and x.shape[0] == args.batch_size:
@@ -172,6 +180,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="host: batches built on the host and copied; "
                              "gpu: uint8 dataset resident on the device, "
                              "batches built by the augmentation kernel")
+    parser.add_argument("--pool_size", default=0, type=int,
+                        help="image history pool: update the discriminators "
+                             "on a buffer of the last N generated images "
+                             "(the CycleGAN paper uses 50); 0: off")
     parser.add_argument("--augment", default="frozen", choices=["frozen", "epoch"],
                         help="frozen: one augmentation per sample for the run "
                              "(the reference's .map().cache()); epoch: re-drawn "
@@ -184,6 +196,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = parser.parse_args(argv)
     if args.augment == "epoch" and args.data_device != "gpu":
         parser.error("--augment epoch requires --data_device gpu")
+    if args.pool_size < 0:
+        parser.error("--pool_size must be >= 0")
     return args
 
 
