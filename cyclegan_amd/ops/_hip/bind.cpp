@@ -68,6 +68,10 @@ std::vector<at::Tensor> persample_loss_bwd(at::Tensor, at::Tensor, at::Tensor,
 at::Tensor persample_loss_const_bwd(at::Tensor, double, at::Tensor, bool);
 void adam_step_dev(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                    double, double, double);
+void adam_ema_step(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                   double, double, double, double, int64_t, double);
+void adam_ema_step_dev(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                       at::Tensor, at::Tensor, double, double, double, double);
 void shadow_gather(at::Tensor, at::Tensor, at::Tensor);
 void adam_step(at::Tensor, at::Tensor, at::Tensor, at::Tensor, double, double,
                double, double, int64_t);
@@ -131,6 +135,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("persample_loss_const_bwd", &cyg::persample_loss_const_bwd);
   m.def("adam_step", &cyg::adam_step);
   m.def("adam_step_dev", &cyg::adam_step_dev);
+  // Adam + weight EMA in one pass (p, m, v bitwise as the two above)
+  m.def("adam_ema_step", &cyg::adam_ema_step);
+  m.def("adam_ema_step_dev", &cyg::adam_ema_step_dev);
   m.def("shadow_gather", &cyg::shadow_gather);
   m.def("augment_batch", &cyg::augment_batch);
   m.def("pool_exchange", &cyg::pool_exchange);

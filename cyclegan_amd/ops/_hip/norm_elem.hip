@@ -661,20 +661,32 @@ __global__ void persample_loss_bwd_kernel(
 }
 
 // ---- fused TF-formula Adam over flat fp32 buffers ----
+// One element's update, shared by every Adam kernel below. Contraction is
+// off: each product, sum, quotient and root rounds once on its own, so
+// the scalar and the 16-byte kernels give the same bits whatever the
+// compiler would otherwise fuse in one loop shape and not in the other
+// (it fused none of this in the scalar loops and all of it in the
+// vectorised one).
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m,
+                                          float& v, float lr_t, float b1,
+                                          float b2, float eps) {
+#pragma clang fp contract(off)
+  float gi = g;
+  float mi = b1 * m + (1.f - b1) * gi;
+  float vi = b2 * v + (1.f - b2) * gi * gi;
+  m = mi;
+  v = vi;
+  p -= lr_t * mi / (sqrtf(vi) + eps);
+}
+
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                             float* __restrict__ m, float* __restrict__ v,
                             long n, float lr_t, float b1, float b2,
                             float eps) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    float gi = g[i];
-    float mi = b1 * m[i] + (1.f - b1) * gi;
-    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= lr_t * mi / (sqrtf(vi) + eps);
-  }
+  for (; i < n; i += stride)
+    adam_elem(p[i], g[i], m[i], v[i], lr_t, b1, b2, eps);
 }
 
 // graph-capture variant: lr_t read from device memory so a captured step
@@ -687,14 +699,63 @@ __global__ void adam_kernel_dev(float* __restrict__ p,
   const float lr_t = *lr_t_ptr;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    float gi = g[i];
-    float mi = b1 * m[i] + (1.f - b1) * gi;
-    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= lr_t * mi / (sqrtf(vi) + eps);
+  for (; i < n; i += stride)
+    adam_elem(p[i], g[i], m[i], v[i], lr_t, b1, b2, eps);
+}
+
+// ---- Adam + exponential moving average of the weights, one pass ----
+// ema = d*ema + (1-d)*p_new rides the Adam walk: the updated p is still in
+// a register, so the average costs its own read and write (8 B/param) and
+// nothing else. The m/v/p arithmetic is adam_elem, the plain kernels'
+// own: p, m, v come out bitwise what they give
+// (tests/test_adam_ema_gpu.py), so switching the average on cannot move
+// the training trajectory.
+__device__ __forceinline__ void adam_ema_elem(float& p, float g, float& m,
+                                              float& v, float& e, float lr_t,
+                                              float b1, float b2, float eps,
+                                              float d, float omd) {
+#pragma clang fp contract(off)
+  adam_elem(p, g, m, v, lr_t, b1, b2, eps);
+  e = d * e + omd * p;
+}
+
+// VEC: 16-byte loads/stores over the first n/4*4 elements (all five
+// pointers 16-byte aligned, checked by the host) and a scalar tail of
+// n%4; !VEC: scalar throughout, for views at an odd storage offset.
+// LR_DEV: lr_t read from device memory (capture-safe, as adam_kernel_dev).
+template <bool VEC, bool LR_DEV>
+__global__ void adam_ema_kernel(float* __restrict__ p,
+                                const float* __restrict__ g,
+                                float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ ema, long n, float lr_imm,
+                                const float* __restrict__ lr_t_ptr, float b1,
+                                float b2, float eps, float d, float omd) {
+  const float lr_t = LR_DEV ? *lr_t_ptr : lr_imm;
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  long done = 0;
+  if (VEC) {
+    const long n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    float4* e4 = reinterpret_cast<float4*>(ema);
+    for (long i = tid; i < n4; i += stride) {
+      float4 pi = p4[i], gi = g4[i], mi = m4[i], vi = v4[i], ei = e4[i];
+      adam_ema_elem(pi.x, gi.x, mi.x, vi.x, ei.x, lr_t, b1, b2, eps, d, omd);
+      adam_ema_elem(pi.y, gi.y, mi.y, vi.y, ei.y, lr_t, b1, b2, eps, d, omd);
+      adam_ema_elem(pi.z, gi.z, mi.z, vi.z, ei.z, lr_t, b1, b2, eps, d, omd);
+      adam_ema_elem(pi.w, gi.w, mi.w, vi.w, ei.w, lr_t, b1, b2, eps, d, omd);
+      m4[i] = mi;
+      v4[i] = vi;
+      p4[i] = pi;
+      e4[i] = ei;
+    }
+    done = n4 << 2;
   }
+  for (long i = done + tid; i < n; i += stride)
+    adam_ema_elem(p[i], g[i], m[i], v[i], ema[i], lr_t, b1, b2, eps, d, omd);
 }
 
 // ================= host wrappers =================
@@ -1116,6 +1177,70 @@ void adam_step_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                      (float*)v.mutable_data_ptr(), n,
                      (const float*)lr_t.const_data_ptr(), (float)b1,
                      (float)b2, (float)eps);
+}
+
+// shared by adam_ema_step / adam_ema_step_dev: checks, path choice, launch
+static void adam_ema_launch(at::Tensor& p, at::Tensor& g, at::Tensor& m,
+                            at::Tensor& v, at::Tensor& ema, float lr_imm,
+                            const float* lr_t_ptr, double b1, double b2,
+                            double eps, double ema_decay) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat);
+  for (const at::Tensor* t : {&p, &g, &m, &v, &ema}) {
+    TORCH_CHECK(t->scalar_type() == at::kFloat, "adam_ema: fp32 only");
+    TORCH_CHECK(t->numel() == p.numel(), "adam_ema: numel mismatch");
+    TORCH_CHECK(t->is_contiguous(), "adam_ema: contiguous only");
+    TORCH_CHECK(t->device() == p.device(), "adam_ema: device mismatch");
+  }
+  TORCH_CHECK(ema_decay >= 0.0 && ema_decay <= 1.0);
+  long n = p.numel();
+  if (n == 0) return;
+  float* pp = (float*)p.mutable_data_ptr();
+  const float* gp = (const float*)g.const_data_ptr();
+  float* mp = (float*)m.mutable_data_ptr();
+  float* vp = (float*)v.mutable_data_ptr();
+  float* ep = (float*)ema.mutable_data_ptr();
+  // a sliced view may start at an odd storage offset: 16-byte accesses
+  // only when every pointer allows them
+  bool vec = ((reinterpret_cast<uintptr_t>(pp) |
+               reinterpret_cast<uintptr_t>(gp) |
+               reinterpret_cast<uintptr_t>(mp) |
+               reinterpret_cast<uintptr_t>(vp) |
+               reinterpret_cast<uintptr_t>(ep)) & 15) == 0;
+  // constants of the run: 1-d in double, then cast (a captured graph
+  // bakes both in)
+  float d = (float)ema_decay, omd = (float)(1.0 - ema_decay);
+  long work = vec ? std::max<long>(n >> 2, n & 3) : n;
+  int blocks = (int)std::min<long>(2048, (work + 255) / 256);
+  auto stream = at::cuda::getCurrentCUDAStream();
+#define CYG_ADAM_EMA(VEC, LRD)                                              \
+  hipLaunchKernelGGL((adam_ema_kernel<VEC, LRD>), dim3(blocks), dim3(256),  \
+                     0, stream, pp, gp, mp, vp, ep, n, lr_imm, lr_t_ptr,    \
+                     (float)b1, (float)b2, (float)eps, d, omd)
+  if (lr_t_ptr) {
+    if (vec) CYG_ADAM_EMA(true, true); else CYG_ADAM_EMA(false, true);
+  } else {
+    if (vec) CYG_ADAM_EMA(true, false); else CYG_ADAM_EMA(false, false);
+  }
+#undef CYG_ADAM_EMA
+}
+
+void adam_ema_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
+                   at::Tensor ema, double lr, double b1, double b2,
+                   double eps, int64_t t, double ema_decay) {
+  // same host arithmetic as adam_step: the immediate must be bit-equal
+  double lr_t = lr * std::sqrt(1.0 - std::pow(b2, (double)t)) /
+                (1.0 - std::pow(b1, (double)t));
+  adam_ema_launch(p, g, m, v, ema, (float)lr_t, nullptr, b1, b2, eps,
+                  ema_decay);
+}
+
+void adam_ema_step_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
+                       at::Tensor ema, at::Tensor lr_t, double b1, double b2,
+                       double eps, double ema_decay) {
+  TORCH_CHECK(lr_t.is_cuda() && lr_t.scalar_type() == at::kFloat &&
+              lr_t.numel() == 1 && lr_t.device() == p.device());
+  adam_ema_launch(p, g, m, v, ema, 0.f, (const float*)lr_t.const_data_ptr(),
+                  b1, b2, eps, ema_decay);
 }
 
 }  // namespace cyg

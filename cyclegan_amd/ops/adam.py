@@ -16,6 +16,15 @@ On MI355X this is ONE kernel per model over the flat buffers (the whole
 generator is a single 11.4M-element update — zero per-tensor launch
 overhead), which also refreshes nothing else: bf16 shadow weights recast
 lazily via the version counter (ops.shadow).
+
+Two optional parts of the CycleGAN recipe live in the same step:
+
+- ``lr_scale`` multiplies ``lr`` everywhere (the trainer sets it once per
+  epoch for the linear decay). In graph mode it reaches the captured kernel
+  through the device ``lr_t`` scalar that advance_lr() rewrites anyway.
+- ``ema_decay`` > 0 keeps ``ema = d*ema + (1-d)*p`` of the parameters, fused
+  into the update kernel (adam_ema_kernel: 8 B/param more, no extra
+  launch). p, m, v are bitwise what they are without it.
 """
 
 from __future__ import annotations
@@ -32,14 +41,20 @@ class FusedAdam:
 
     def __init__(self, flat_param: torch.Tensor, flat_grad: torch.Tensor,
                  lr: float = 2e-4, beta1: float = 0.5, beta2: float = 0.9,
-                 eps: float = 1e-7):
+                 eps: float = 1e-7, ema_decay: float = 0.0):
         assert flat_param.dtype == torch.float32
+        assert 0.0 <= ema_decay < 1.0
         self.p = flat_param
         self.g = flat_grad
         self.lr, self.b1, self.b2, self.eps = lr, beta1, beta2, eps
         self.m = torch.zeros_like(flat_param)
         self.v = torch.zeros_like(flat_param)
         self.t = 0
+        # schedule factor on lr; derived from the epoch, so not in state_dict
+        self.lr_scale = 1.0
+        # exponential moving average of the parameters (None: off)
+        self.ema_decay = float(ema_decay)
+        self.ema = flat_param.detach().clone() if ema_decay > 0 else None
         # graph-capture mode: the update kernel reads lr_t from this device
         # scalar instead of an immediate, so a captured step follows the
         # per-step bias correction written by advance_lr() before replay
@@ -47,8 +62,15 @@ class FusedAdam:
         self._lr_t_dev = None
 
     def _lr_t(self) -> float:
-        return (self.lr * math.sqrt(1 - self.b2 ** self.t)
+        return (self.lr * self.lr_scale * math.sqrt(1 - self.b2 ** self.t)
                 / (1 - self.b1 ** self.t))
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """Restart the average from the current parameters (after loading
+        weights that come without one)."""
+        if self.ema is not None:
+            self.ema.copy_(self.p)
 
     @torch.no_grad()
     def prepare_graph(self):
@@ -73,24 +95,38 @@ class FusedAdam:
     def step(self):
         if self.graph_mode:
             # t/lr_t advanced by advance_lr(); capture-safe kernel
+            if self.ema is not None:
+                backend.ext().adam_ema_step_dev(
+                    self.p, self.g, self.m, self.v, self.ema, self._lr_t_dev,
+                    self.b1, self.b2, self.eps, self.ema_decay)
+                return
             backend.ext().adam_step_dev(self.p, self.g, self.m, self.v,
                                         self._lr_t_dev, self.b1, self.b2,
                                         self.eps)
             return
         self.t += 1
         if backend.use_hip(self.p):
-            backend.ext().adam_step(self.p, self.g, self.m, self.v,
-                                    self.lr, self.b1, self.b2, self.eps, self.t)
+            lr = self.lr * self.lr_scale
+            if self.ema is not None:
+                backend.ext().adam_ema_step(
+                    self.p, self.g, self.m, self.v, self.ema, lr, self.b1,
+                    self.b2, self.eps, self.t, self.ema_decay)
+            else:
+                backend.ext().adam_step(self.p, self.g, self.m, self.v,
+                                        lr, self.b1, self.b2, self.eps, self.t)
             # the raw kernel bypasses the dispatcher, so the in-place update
             # does not bump the version counter that invalidates the bf16
             # shadow-weight caches (ops.shadow) — bump it explicitly, or
             # compute would keep running on the step-0 weights forever
             torch.autograd.graph.increment_version(self.p)
             return
-        lr_t = self.lr * math.sqrt(1 - self.b2 ** self.t) / (1 - self.b1 ** self.t)
+        lr_t = (self.lr * self.lr_scale * math.sqrt(1 - self.b2 ** self.t)
+                / (1 - self.b1 ** self.t))
         self.m.mul_(self.b1).add_(self.g, alpha=1 - self.b1)
         self.v.mul_(self.b2).addcmul_(self.g, self.g, value=1 - self.b2)
         self.p.addcdiv_(self.m, self.v.sqrt().add_(self.eps), value=-lr_t)
+        if self.ema is not None:
+            self.ema.mul_(self.ema_decay).add_(self.p, alpha=1 - self.ema_decay)
 
     def state_dict(self):
         return {"m": self.m, "v": self.v, "t": self.t,

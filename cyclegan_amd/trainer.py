@@ -28,6 +28,7 @@ on the MI355X execution model:
 
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Dict, Optional
 
@@ -37,6 +38,19 @@ from .models import Generator, Discriminator
 from .ops import MAE, MSE, MSE_const, ImagePool, backend, grad_sink
 from .ops.adam import FusedAdam
 from .parallel import DistContext, GradSync, FlatParamGroup
+
+
+def lr_factor(epoch: int, epochs: int, decay_epochs: int) -> float:
+    """Learning-rate factor of 0-based ``epoch`` in a run of ``epochs``:
+    1 for the first ``epochs - decay_epochs`` epochs, then linear towards
+    zero over the last ``decay_epochs`` — the schedule of the CycleGAN
+    authors' public implementation with n_epochs = epochs - decay_epochs.
+    It steps once per epoch, is 1/(decay_epochs+1) in the last epoch and
+    never reaches 0 inside the run; decay_epochs == 0 gives 1 always."""
+    if decay_epochs <= 0:
+        return 1.0
+    f = 1.0 - max(0, epoch - (epochs - decay_epochs) + 1) / (decay_epochs + 1)
+    return min(1.0, max(0.0, f))
 
 
 class CycleGAN:
@@ -72,8 +86,14 @@ class CycleGAN:
 
         self.groups = {name: FlatParamGroup(m) for name, m in
                        (("G", self.G), ("F", self.F), ("X", self.X), ("Y", self.Y))}
-        self.optimizers = {name: FusedAdam(g.flat_param, g.flat_grad)
-                           for name, g in self.groups.items()}
+        # averaged generator weights (ema_decay > 0): kept by G's and F's
+        # optimizers only, the discriminators never run at inference
+        self.ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
+        self.lr_decay_epochs = int(getattr(args, "lr_decay_epochs", 0) or 0)
+        self.optimizers = {
+            name: FusedAdam(g.flat_param, g.flat_grad,
+                            ema_decay=self.ema_decay if name in "GF" else 0.0)
+            for name, g in self.groups.items()}
         self.sync = GradSync(ctx, timing=getattr(args, "verbose", 1) == 2)
 
         # shadow arenas: every bf16 compute form of a group refreshed by
@@ -107,6 +127,68 @@ class CycleGAN:
     def _refresh_shadows(self):
         for a in self.arenas.values():
             a.refresh()
+
+    # ---- learning-rate schedule, averaged generator weights ----
+
+    def set_lr_scale(self, s: float):
+        """Schedule factor on every optimizer's lr. A captured step picks
+        it up through the device lr_t scalar (FusedAdam.advance_lr)."""
+        for opt in self.optimizers.values():
+            opt.lr_scale = float(s)
+
+    @torch.no_grad()
+    def _exchange_ema(self):
+        for name in ("G", "F"):
+            p, ema = self.groups[name].flat_param, self.optimizers[name].ema
+            tmp = p.clone()
+            p.copy_(ema)
+            ema.copy_(tmp)
+            self.groups[name].bump_versions()
+        self._refresh_shadows()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate with the averaged generators: inside, G and F compute
+        with the EMA weights; on exit (also on an exception) the live
+        weights are back, both buffers bitwise as before. The CONTENTS of
+        flat_param and ema are exchanged, never the pointers: the captured
+        graph, the parameter views and the shadow arenas hold the
+        addresses. A no-op with the average off."""
+        if not self.ema_decay:
+            yield
+            return
+        assert not (self.device.type == "cuda"
+                    and torch.cuda.is_current_stream_capturing()), \
+            "ema_weights() inside a graph capture"
+        self._exchange_ema()
+        try:
+            yield
+        finally:
+            self._exchange_ema()
+
+    def _ema_state_dict(self, name: str):
+        """The averaged weights of G or F in module state_dict format:
+        parameters viewed out of the flat average through the group's
+        offsets, buffers taken from the live module."""
+        module, group = getattr(self, name), self.groups[name]
+        ema = self.optimizers[name].ema
+        views = {id(p): ema[off:off + k].view(p.shape)
+                 for p, (off, k) in zip(group.params, group._offsets)}
+        sd = module.state_dict()
+        for key, p in module.named_parameters():
+            if id(p) in views:
+                sd[key] = views[id(p)]
+        return sd
+
+    @torch.no_grad()
+    def _load_ema_state_dict(self, name: str, sd):
+        module, group = getattr(self, name), self.groups[name]
+        ema = self.optimizers[name].ema
+        offs = {id(p): ok for p, ok in zip(group.params, group._offsets)}
+        for key, p in module.named_parameters():
+            if id(p) in offs:
+                off, k = offs[id(p)]
+                ema[off:off + k].copy_(sd[key].reshape(-1))
 
     # ---- image history pool ----
 
@@ -398,6 +480,9 @@ class CycleGAN:
                 "X_optimizer": self.optimizers["X"].state_dict(),
                 "Y_optimizer": self.optimizers["Y"].state_dict(),
             }
+            if self.ema_decay:
+                state["G_ema"] = self._ema_state_dict("G")
+                state["F_ema"] = self._ema_state_dict("F")
             if self.pools is not None:  # this rank's; ranks are not synced
                 state["pool_x"] = self.pools[0].state_dict()
                 state["pool_y"] = self.pools[1].state_dict()
@@ -418,6 +503,15 @@ class CycleGAN:
         self.Y.load_state_dict(state["Y"])
         for name in ("G", "F", "X", "Y"):
             self.optimizers[name].load_state_dict(state[f"{name}_optimizer"])
+        if self.ema_decay:
+            # a checkpoint without averages restarts them from the weights
+            # just loaded (the construction-time copy holds the random
+            # init); with the average off, saved ones are ignored
+            for name in ("G", "F"):
+                if f"{name}_ema" in state:
+                    self._load_ema_state_dict(name, state[f"{name}_ema"])
+                else:
+                    self.optimizers[name].reset_ema()
         if self.pool_size and "pool_x" in state:
             # a checkpoint without pools starts them empty; with the pool
             # off, saved pools are ignored
@@ -479,6 +573,9 @@ class GraphedStep:
             saved = {n: (g.flat_param.clone(), gan.optimizers[n].m.clone(),
                          gan.optimizers[n].v.clone(), gan.optimizers[n].t)
                      for n, g in gan.groups.items()}
+            # the warm-up steps must not leak into the weight average
+            saved_ema = {n: o.ema.clone() for n, o in gan.optimizers.items()
+                         if o.ema is not None}
             saved_pools = [p.state_dict() for p in gan.pools or ()]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -503,6 +600,8 @@ class GraphedStep:
                     gan.optimizers[n].m.copy_(m)
                     gan.optimizers[n].v.copy_(v)
                     gan.optimizers[n].t = t
+                for n, e in saved_ema.items():
+                    gan.optimizers[n].ema.copy_(e)
                 for p, state in zip(gan.pools or (), saved_pools):
                     p.load_state_dict(state)
                 gan._refresh_shadows()
@@ -552,6 +651,9 @@ class SegmentedGraphedStep:
             saved = {n: (g.flat_param.clone(), gan.optimizers[n].m.clone(),
                          gan.optimizers[n].v.clone(), gan.optimizers[n].t)
                      for n, g in gan.groups.items()}
+            # the warm-up steps must not leak into the weight average
+            saved_ema = {n: o.ema.clone() for n, o in gan.optimizers.items()
+                         if o.ema is not None}
             saved_pools = [p.state_dict() for p in gan.pools or ()]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -596,6 +698,8 @@ class SegmentedGraphedStep:
                     gan.optimizers[n].m.copy_(m)
                     gan.optimizers[n].v.copy_(v)
                     gan.optimizers[n].t = t
+                for n, e in saved_ema.items():
+                    gan.optimizers[n].ema.copy_(e)
                 for p, state in zip(gan.pools or (), saved_pools):
                     p.load_state_dict(state)
                 gan._refresh_shadows()

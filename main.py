@@ -13,7 +13,13 @@ keeps the dataset on the device as uint8 and builds every batch with one
 augmentation kernel (data/device.py); --augment epoch re-draws the
 augmentation each epoch (device path only). --pool_size N updates the
 discriminators on a history of N generated images (the CycleGAN paper's
-image pool, N = 50 there; ops/pool.py).
+image pool, N = 50 there; ops/pool.py). --lr_decay_epochs N decays the
+learning rate linearly towards zero over the last N epochs (the paper:
+N = epochs/2), stepping once per epoch; a resumed run picks the schedule
+up at the epoch the optimizer's step count implies. --ema_decay D keeps an
+exponential moving average of the generator weights inside the fused Adam
+kernel; the test epoch, the cycle plots and ``translate.py --ema`` then use
+the averaged generators.
 """
 
 from __future__ import annotations
@@ -28,7 +34,7 @@ import torch
 from tqdm import tqdm
 
 from cyclegan_amd.parallel import DistContext
-from cyclegan_amd.trainer import CycleGAN
+from cyclegan_amd.trainer import CycleGAN, lr_factor
 from cyclegan_amd.data import Pipeline, DevicePipeline, DevicePrefetcher
 from cyclegan_amd import utils
 
@@ -78,10 +84,11 @@ def test(args, pipe, gan, summary, epoch: int):
     it = pipe.test_epoch()
     if args.data_device != "gpu":
         it = DevicePrefetcher(it, gan.device, gan.compute_dtype)
-    for x, y in tqdm(it, desc="Test", total=pipe.test_steps,
-                     disable=args.verbose == 0 or not gan.ctx.is_main):
-        result = gan.test_step(x, y)
-        utils.append_dict(results, result)
+    with gan.ema_weights():  # the averaged generators, when kept
+        for x, y in tqdm(it, desc="Test", total=pipe.test_steps,
+                         disable=args.verbose == 0 or not gan.ctx.is_main):
+            result = gan.test_step(x, y)
+            utils.append_dict(results, result)
     reduced = gan.reduce_results(results)
     if summary is not None:
         for key, value in reduced.items():
@@ -122,9 +129,22 @@ def main(args):
     gan = CycleGAN(args, ctx)
     gan.load_checkpoint()
 
-    for epoch in range(args.epochs):
+    # a schedule that restarted on resume would be wrong: with the decay
+    # on, go on at the epoch the restored optimizer step count implies
+    first_epoch = 0
+    if args.lr_decay_epochs > 0:
+        first_epoch = gan.optimizers["G"].t // pipe.train_steps
+
+    for epoch in range(first_epoch, args.epochs):
         if ctx.is_main:
             print(f"Epoch {epoch + 1:03d}/{args.epochs:03d}")
+        if args.lr_decay_epochs > 0:
+            scale = lr_factor(epoch, args.epochs, args.lr_decay_epochs)
+            gan.set_lr_scale(scale)
+            if summary is not None:
+                summary.scalar("learning_rate",
+                               gan.optimizers["G"].lr * scale, step=epoch,
+                               training=True)
 
         start = time()
         train(args, pipe, gan, summary, epoch)
@@ -150,7 +170,8 @@ def main(args):
         if epoch % 10 == 0 or epoch == args.epochs - 1:
             gan.save_checkpoint()
             if ctx.is_main:
-                utils.plot_cycle(pipe.plot_pairs(), gan, summary, epoch)
+                with gan.ema_weights():
+                    utils.plot_cycle(pipe.plot_pairs(), gan, summary, epoch)
             ctx.barrier()
 
     if summary is not None:
@@ -184,6 +205,14 @@ def build_parser() -> argparse.ArgumentParser:
                         help="image history pool: update the discriminators "
                              "on a buffer of the last N generated images "
                              "(the CycleGAN paper uses 50); 0: off")
+    parser.add_argument("--lr_decay_epochs", default=0, type=int,
+                        help="decay the learning rate linearly towards zero "
+                             "over the last N epochs (the CycleGAN paper: "
+                             "half the run); 0: constant")
+    parser.add_argument("--ema_decay", default=0.0, type=float,
+                        help="keep an exponential moving average of the "
+                             "generator weights with this decay (e.g. 0.999) "
+                             "and evaluate with it; 0: off")
     parser.add_argument("--augment", default="frozen", choices=["frozen", "epoch"],
                         help="frozen: one augmentation per sample for the run "
                              "(the reference's .map().cache()); epoch: re-drawn "
@@ -198,6 +227,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("--augment epoch requires --data_device gpu")
     if args.pool_size < 0:
         parser.error("--pool_size must be >= 0")
+    if not 0 <= args.lr_decay_epochs <= args.epochs:
+        parser.error("--lr_decay_epochs must be in [0, --epochs]")
+    if not 0.0 <= args.ema_decay < 1.0:
+        parser.error("--ema_decay must be in [0, 1)")
     return args
 
 

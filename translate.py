@@ -6,6 +6,8 @@
 Loads G (x->y) or F (y->x) from a framework checkpoint and writes
 translated PNGs. Accepts an image folder or, with --synthetic N, random
 inputs (useful without data). Runs the same HIP kernel path as training.
+--ema translates with the averaged generator weights that a run trained
+with ``main.py --ema_decay D`` saves beside the live ones.
 """
 
 from __future__ import annotations
@@ -30,6 +32,8 @@ def main():
     ap.add_argument("--image_size", type=int, default=256)
     ap.add_argument("--num_residual_blocks", type=int, default=9)
     ap.add_argument("--batch_size", type=int, default=8)
+    ap.add_argument("--ema", action="store_true",
+                    help="use the averaged generator weights (G_ema/F_ema)")
     args = ap.parse_args()
 
     device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
@@ -37,7 +41,13 @@ def main():
 
     gen = Generator(num_residual_blocks=args.num_residual_blocks).to(device)
     state = torch.load(args.checkpoint, map_location=device, weights_only=True)
-    gen.load_state_dict(state["G" if args.direction == "x2y" else "F"])
+    key = "G" if args.direction == "x2y" else "F"
+    if args.ema:
+        key += "_ema"
+        if key not in state:
+            raise SystemExit(f"{args.checkpoint} holds no averaged weights "
+                             f"({key}): train with --ema_decay D to save them")
+    gen.load_state_dict(state[key])
     gen.eval()
 
     if args.input_dir:
