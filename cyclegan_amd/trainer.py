@@ -56,6 +56,8 @@ def lr_factor(epoch: int, epochs: int, decay_epochs: int) -> float:
 class CycleGAN:
     LAMBDA_CYCLE = 10.0
     LAMBDA_IDENTITY = 0.5 * 10.0
+    # the four models, in optimizer and collective order
+    _NAMES = ("G", "F", "X", "Y")
 
     def __init__(self, args, ctx: DistContext):
         self.ctx = ctx
@@ -84,8 +86,8 @@ class CycleGAN:
         for m in (self.G, self.F, self.X, self.Y):
             ctx.broadcast_module(m)
 
-        self.groups = {name: FlatParamGroup(m) for name, m in
-                       (("G", self.G), ("F", self.F), ("X", self.X), ("Y", self.Y))}
+        self.groups = {name: FlatParamGroup(getattr(self, name))
+                       for name in self._NAMES}
         # averaged generator weights (ema_decay > 0): kept by G's and F's
         # optimizers only, the discriminators never run at inference
         self.ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
@@ -104,9 +106,8 @@ class CycleGAN:
                 and backend.load_ext() is not None):
             from .ops.arena import ShadowArena
             from .ops import shadow as _shadow
-            for name, m in (("G", self.G), ("F", self.F),
-                            ("X", self.X), ("Y", self.Y)):
-                a = ShadowArena(self.groups[name], m)
+            for name in self._NAMES:
+                a = ShadowArena(self.groups[name], getattr(self, name))
                 _shadow.register_arena(a)
                 self.arenas[name] = a
 
@@ -127,6 +128,32 @@ class CycleGAN:
     def _refresh_shadows(self):
         for a in self.arenas.values():
             a.refresh()
+
+    def _snapshot_state(self):
+        """Everything a train step may touch, for _restore_state: flat
+        params and Adam m/v/t of every group, the weight averages (warm-up
+        steps must not leak into them), the pools."""
+        opts = self.optimizers
+        return ({n: (g.flat_param.clone(), opts[n].m.clone(),
+                     opts[n].v.clone(), opts[n].t)
+                 for n, g in self.groups.items()},
+                {n: o.ema.clone() for n, o in opts.items()
+                 if o.ema is not None},
+                [p.state_dict() for p in self.pools or ()])
+
+    @torch.no_grad()
+    def _restore_state(self, saved):
+        state, emas, pools = saved
+        for n, (p, m, v, t) in state.items():
+            self.groups[n].flat_param.copy_(p)
+            self.optimizers[n].m.copy_(m)
+            self.optimizers[n].v.copy_(v)
+            self.optimizers[n].t = t
+        for n, e in emas.items():
+            self.optimizers[n].ema.copy_(e)
+        for p, s in zip(self.pools or (), pools):
+            p.load_state_dict(s)
+        self._refresh_shadows()
 
     # ---- learning-rate schedule, averaged generator weights ----
 
@@ -286,11 +313,9 @@ class CycleGAN:
             g.flat_grad.zero_()
             self.sync.launch(g.flat_grad)
         self.sync.wait_all()
-        for opt in self.optimizers.values():
-            opt.step()
-        for g in self.groups.values():
-            g.bump_versions()
-        self._refresh_shadows()
+        # no fp8 amax roll: the empty slice recorded no amax, and
+        # prev <- cur would zero prev
+        self._optimize(roll_amax=False)
         return self._zero_losses(self._TRAIN_KEYS)
 
     def _forward_losses(self, x, y) -> Dict[str, torch.Tensor]:
@@ -330,14 +355,8 @@ class CycleGAN:
         F_cycle_loss = self.cycle_loss(x, cycle_x)
         G_identity_loss = self.identity_loss(y, same_y)
         F_identity_loss = self.identity_loss(x, same_x)
-        losses = {
-            "loss_G/loss": G_loss, "loss_G/cycle": G_cycle_loss,
-            "loss_G/identity": G_identity_loss,
-            "loss_G/total": G_loss + G_cycle_loss + G_identity_loss,
-            "loss_F/loss": F_loss, "loss_F/cycle": F_cycle_loss,
-            "loss_F/identity": F_identity_loss,
-            "loss_F/total": F_loss + F_cycle_loss + F_identity_loss,
-        }
+        losses = self._loss_dict(G_loss, G_cycle_loss, G_identity_loss,
+                                 F_loss, F_cycle_loss, F_identity_loss)
         if self.pool_size:
             # history pool: the discriminators train on exchanged fakes,
             # so their pass over the fake is no longer the generators' one
@@ -350,8 +369,25 @@ class CycleGAN:
                 self.Y(y), discriminate_fake_y)
         return losses
 
-    _GROUP_LOSS = (("G", "loss_G/total"), ("F", "loss_F/total"),
-                   ("X", "loss_X/loss"), ("Y", "loss_Y/loss"))
+    @staticmethod
+    def _loss_dict(G_loss, G_cycle, G_identity, F_loss, F_cycle,
+                   F_identity) -> Dict[str, torch.Tensor]:
+        """The loss dict of a step from the six generator terms, in
+        _TRAIN_KEYS order. The caller adds loss_X/loss and loss_Y/loss
+        afterwards: the totals are summed here, before the discriminators
+        see the real images, which is where the step has always launched
+        those additions."""
+        return {
+            "loss_G/loss": G_loss, "loss_G/cycle": G_cycle,
+            "loss_G/identity": G_identity,
+            "loss_G/total": G_loss + G_cycle + G_identity,
+            "loss_F/loss": F_loss, "loss_F/cycle": F_cycle,
+            "loss_F/identity": F_identity,
+            "loss_F/total": F_loss + F_cycle + F_identity,
+        }
+
+    _GROUP_LOSS = tuple(zip(_NAMES, ("loss_G/total", "loss_F/total",
+                                     "loss_X/loss", "loss_Y/loss")))
 
     def _grads_for(self, losses: Dict[str, torch.Tensor], name: str,
                    retain: bool):
@@ -384,13 +420,15 @@ class CycleGAN:
         pooled fakes are detached), each pass may free its own."""
         return i < 3 and not self.pool_size
 
-    def _optimize(self):
+    def _optimize(self, roll_amax: bool = True):
+        """The optimizer stage of every step driver (eager, empty slice,
+        both graph steps): nothing else steps the optimizers."""
         for opt in self.optimizers.values():
             opt.step()
         for g in self.groups.values():
             g.bump_versions()  # invalidate bf16 shadow caches (see flat.py)
         self._refresh_shadows()
-        if getattr(self, "_fp8", False):
+        if self._fp8 and roll_amax:
             from .ops import fp8_state
             fp8_state.roll()  # delayed-scaling amax: prev <- cur
 
@@ -410,19 +448,7 @@ class CycleGAN:
             self.sync.launch(self.groups[name].flat_grad)
         self.sync.wait_all()
         self._optimize()
-        G_loss = losses["loss_G/loss"]; G_cycle_loss = losses["loss_G/cycle"]
-        G_identity_loss = losses["loss_G/identity"]; G_total = losses["loss_G/total"]
-        F_loss = losses["loss_F/loss"]; F_cycle_loss = losses["loss_F/cycle"]
-        F_identity_loss = losses["loss_F/identity"]; F_total = losses["loss_F/total"]
-        X_loss = losses["loss_X/loss"]; Y_loss = losses["loss_Y/loss"]
-
-        return {
-            "loss_G/loss": G_loss.detach(), "loss_G/cycle": G_cycle_loss.detach(),
-            "loss_G/identity": G_identity_loss.detach(), "loss_G/total": G_total.detach(),
-            "loss_F/loss": F_loss.detach(), "loss_F/cycle": F_cycle_loss.detach(),
-            "loss_F/identity": F_identity_loss.detach(), "loss_F/total": F_total.detach(),
-            "loss_X/loss": X_loss.detach(), "loss_Y/loss": Y_loss.detach(),
-        }
+        return {k: losses[k].detach() for k in self._TRAIN_KEYS}
 
     @torch.no_grad()
     def cycle_step(self, x, y, training: bool = False):
@@ -450,17 +476,13 @@ class CycleGAN:
         same_y = self.G(y)
         G_identity_loss = self.identity_loss(y, same_y)
         F_identity_loss = self.identity_loss(x, same_x)
-        G_total = G_loss + G_cycle_loss + G_identity_loss
-        F_total = F_loss + F_cycle_loss + F_identity_loss
+        losses = self._loss_dict(G_loss, G_cycle_loss, G_identity_loss,
+                                 F_loss, F_cycle_loss, F_identity_loss)
         X_loss = self.discriminator_loss(self.X(x), discriminate_fake_x)
         Y_loss = self.discriminator_loss(self.Y(y), discriminate_fake_y)
 
         return {
-            "loss_G/loss": G_loss, "loss_G/cycle": G_cycle_loss,
-            "loss_G/identity": G_identity_loss, "loss_G/total": G_total,
-            "loss_F/loss": F_loss, "loss_F/cycle": F_cycle_loss,
-            "loss_F/identity": F_identity_loss, "loss_F/total": F_total,
-            "loss_X/loss": X_loss, "loss_Y/loss": Y_loss,
+            **losses, "loss_X/loss": X_loss, "loss_Y/loss": Y_loss,
             "error/MAE(X, F(G(X)))": self.reduce_mean(MAE(x, cycle_x)),
             "error/MAE(Y, G(F(Y)))": self.reduce_mean(MAE(y, cycle_y)),
             "error/MAE(X, F(X))": self.reduce_mean(MAE(x, same_x)),
@@ -472,14 +494,9 @@ class CycleGAN:
 
     def save_checkpoint(self):
         if self.ctx.is_main:
-            state = {
-                "G": self.G.state_dict(), "F": self.F.state_dict(),
-                "X": self.X.state_dict(), "Y": self.Y.state_dict(),
-                "G_optimizer": self.optimizers["G"].state_dict(),
-                "F_optimizer": self.optimizers["F"].state_dict(),
-                "X_optimizer": self.optimizers["X"].state_dict(),
-                "Y_optimizer": self.optimizers["Y"].state_dict(),
-            }
+            state = {n: getattr(self, n).state_dict() for n in self._NAMES}
+            for n in self._NAMES:
+                state[f"{n}_optimizer"] = self.optimizers[n].state_dict()
             if self.ema_decay:
                 state["G_ema"] = self._ema_state_dict("G")
                 state["F_ema"] = self._ema_state_dict("F")
@@ -497,11 +514,9 @@ class CycleGAN:
             return False
         state = torch.load(self.checkpoint_path, map_location=self.device,
                            weights_only=True)
-        self.G.load_state_dict(state["G"])
-        self.F.load_state_dict(state["F"])
-        self.X.load_state_dict(state["X"])
-        self.Y.load_state_dict(state["Y"])
-        for name in ("G", "F", "X", "Y"):
+        for name in self._NAMES:
+            getattr(self, name).load_state_dict(state[name])
+        for name in self._NAMES:
             self.optimizers[name].load_state_dict(state[f"{name}_optimizer"])
         if self.ema_decay:
             # a checkpoint without averages restarts them from the weights
@@ -536,14 +551,71 @@ class CycleGAN:
         return dict(zip(keys, vals))
 
 
-class GraphedStep:
+class _GraphStep:
+    """What the two graph steps share: static inputs and pool codes,
+    warm-up, the state roll-back after the capture, and everything a
+    replay does around its graph launches. A subclass captures in
+    ``_capture`` (which sets ``out`` and ``_packed``) and launches in
+    ``_replay``."""
+
+    def __init__(self, gan: CycleGAN, x: torch.Tensor, y: torch.Tensor,
+                 warmup: int = 2, preserve_state: bool = False):
+        assert gan.ctx.device.type == "cuda"
+        self.gan = gan
+        self.sx = gan._cast(x).clone()
+        self.sy = gan._cast(y).clone()
+        # history pool: static codes, all-pass through warm-up and capture
+        self.codes = gan._static_codes = gan.static_pool_codes(self.sx)
+        # preserve_state: roll model/optimizer state back after the warmup
+        # steps so capturing mid-training perturbs nothing (main.py uses
+        # this to capture on the first batch of an epoch)
+        saved = gan._snapshot_state() if preserve_state else None
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                gan.train_step(self.sx, self.sy)
+        torch.cuda.current_stream().wait_stream(s)
+        for opt in gan.optimizers.values():
+            opt.prepare_graph()
+        # capture records the kernel sequence without executing it: the
+        # optimizer step count is NOT advanced here, so replay #1 runs the
+        # exact t the eager path would
+        self._capture()
+        gan._static_codes = None  # eager steps draw for themselves again
+        if saved is not None:
+            gan._restore_state(saved)
+
+    def __call__(self, x=None, y=None) -> Dict[str, torch.Tensor]:
+        gan = self.gan
+        if x is not None:
+            self.sx.copy_(gan._cast(x))
+            self.sy.copy_(gan._cast(y))
+        for opt in gan.optimizers.values():
+            opt.advance_lr()
+        if self.codes is not None:
+            gan.refresh_pool_codes(self.codes)
+        self._replay()
+        for g in gan.groups.values():
+            g.bump_versions()
+        return self.out
+
+    def call_cloned(self, x, y) -> Dict[str, torch.Tensor]:
+        """Replay and return loss scalars detached from the static graph
+        outputs (ONE clone kernel), safe to accumulate across steps."""
+        self(x, y)
+        p = self._packed.clone()
+        return {k: p[i] for i, k in enumerate(self.gan._TRAIN_KEYS)}
+
+
+class GraphedStep(_GraphStep):
     """The steady-state train step captured as ONE hip graph.
 
     The whole step — bf16 shadow recasts, batched G/F/D forwards, the four
     backward passes, flat-grad copies and the four fused Adam updates —
     replays as a single graph launch, eliminating the per-kernel host
     launch gaps of ~300 small launches (the reference leans on TF's
-    tracing compiler for the same effect, /root/reference/main.py:198-205;
+    tracing compiler for the same effect, reference main.py:198-205;
     the MI355X-native equivalent is hipGraph capture).
 
     Requirements: static shapes, CUDA device, world_size == 1 (RCCL graph
@@ -560,74 +632,20 @@ class GraphedStep:
         assert gan.ctx.device.type == "cuda" and (
             gan.ctx.world_size == 1
             or os.environ.get("CYG_GRAPH_DIST") == "1")
-        self.gan = gan
-        self.sx = gan._cast(x).clone()
-        self.sy = gan._cast(y).clone()
-        # history pool: static codes, all-pass through warm-up and capture
-        self.codes = gan._static_codes = gan.static_pool_codes(self.sx)
-        # preserve_state: roll model/optimizer state back after the warmup
-        # steps so capturing mid-training perturbs nothing (main.py uses
-        # this to capture on the first batch of an epoch)
-        saved = None
-        if preserve_state:
-            saved = {n: (g.flat_param.clone(), gan.optimizers[n].m.clone(),
-                         gan.optimizers[n].v.clone(), gan.optimizers[n].t)
-                     for n, g in gan.groups.items()}
-            # the warm-up steps must not leak into the weight average
-            saved_ema = {n: o.ema.clone() for n, o in gan.optimizers.items()
-                         if o.ema is not None}
-            saved_pools = [p.state_dict() for p in gan.pools or ()]
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                gan.train_step(self.sx, self.sy)
-        torch.cuda.current_stream().wait_stream(s)
-        for opt in gan.optimizers.values():
-            opt.prepare_graph()
-        # capture records the kernel sequence without executing it: the
-        # optimizer step count is NOT advanced here, so replay #1 runs the
-        # exact t the eager path would
+        super().__init__(gan, x, y, warmup, preserve_state)
+
+    def _capture(self):
+        gan = self.gan
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.out = gan.train_step(self.sx, self.sy)
-            self._packed = torch.stack([self.out[k] for k in self.gan._TRAIN_KEYS])
-        gan._static_codes = None  # eager steps draw for themselves again
-        if saved is not None:
-            with torch.no_grad():
-                for n, (p, m, v, t) in saved.items():
-                    gan.groups[n].flat_param.copy_(p)
-                    gan.optimizers[n].m.copy_(m)
-                    gan.optimizers[n].v.copy_(v)
-                    gan.optimizers[n].t = t
-                for n, e in saved_ema.items():
-                    gan.optimizers[n].ema.copy_(e)
-                for p, state in zip(gan.pools or (), saved_pools):
-                    p.load_state_dict(state)
-                gan._refresh_shadows()
+            self._packed = torch.stack([self.out[k] for k in gan._TRAIN_KEYS])
 
-    def __call__(self, x=None, y=None) -> Dict[str, torch.Tensor]:
-        if x is not None:
-            self.sx.copy_(self.gan._cast(x))
-            self.sy.copy_(self.gan._cast(y))
-        for opt in self.gan.optimizers.values():
-            opt.advance_lr()
-        if self.codes is not None:
-            self.gan.refresh_pool_codes(self.codes)
+    def _replay(self):
         self.graph.replay()
-        for g in self.gan.groups.values():
-            g.bump_versions()
-        return self.out
-
-    def call_cloned(self, x, y) -> Dict[str, torch.Tensor]:
-        """Replay and return loss scalars detached from the static graph
-        outputs (ONE clone kernel), safe to accumulate across steps."""
-        self(x, y)
-        p = self._packed.clone()
-        return {k: p[i] for i, k in enumerate(self.gan._TRAIN_KEYS)}
 
 
-class SegmentedGraphedStep:
+class SegmentedGraphedStep(_GraphStep):
     """Multi-rank graph step: the step is captured as FIVE RCCL-free hip
     graphs (forward + G-grads, F-grads, X-grads, Y-grads, optimizers)
     sharing one capture pool, and the four flat-gradient all-reduces are
@@ -638,91 +656,28 @@ class SegmentedGraphedStep:
     path exactly (G, F, X, Y), so graphed and eager/empty-slice ranks
     interoperate."""
 
-    def __init__(self, gan: CycleGAN, x: torch.Tensor, y: torch.Tensor,
-                 warmup: int = 2, preserve_state: bool = False):
-        assert gan.ctx.device.type == "cuda"
-        self.gan = gan
-        self.sx = gan._cast(x).clone()
-        self.sy = gan._cast(y).clone()
-        # history pool: static codes, all-pass through warm-up and capture
-        self.codes = gan._static_codes = gan.static_pool_codes(self.sx)
-        saved = None
-        if preserve_state:
-            saved = {n: (g.flat_param.clone(), gan.optimizers[n].m.clone(),
-                         gan.optimizers[n].v.clone(), gan.optimizers[n].t)
-                     for n, g in gan.groups.items()}
-            # the warm-up steps must not leak into the weight average
-            saved_ema = {n: o.ema.clone() for n, o in gan.optimizers.items()
-                         if o.ema is not None}
-            saved_pools = [p.state_dict() for p in gan.pools or ()]
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                gan.train_step(self.sx, self.sy)
-        torch.cuda.current_stream().wait_stream(s)
-        for opt in gan.optimizers.values():
-            opt.prepare_graph()
-
-        self.names = [n for n, _ in gan._GROUP_LOSS]
-        self.graphs = []
+    def _capture(self):
+        gan = self.gan
         gan._step_codes = self.codes  # train_step's part, skipped below
-        g1 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1):
-            losses = gan._forward_losses(self.sx, self.sy)
-            gan._grads_for(losses, "G", retain=gan._retain(0))
-        self.graphs.append(g1)
-        pool = g1.pool()
-        for i, name in enumerate(self.names[1:], start=1):
-            g = torch.cuda.CUDAGraph()
+        self.grad_graphs, pool = {}, None
+        for i, name in enumerate(gan._NAMES):
+            g = self.grad_graphs[name] = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool):
+                if i == 0:  # the forward rides in G's graph
+                    losses = gan._forward_losses(self.sx, self.sy)
                 gan._grads_for(losses, name, retain=gan._retain(i))
-            self.graphs.append(g)
-        gopt = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gopt, pool=pool):
-            for opt in gan.optimizers.values():
-                opt.step()
-            gan._refresh_shadows()
-            if getattr(gan, "_fp8", False):
-                from .ops import fp8_state
-                fp8_state.roll()
+            pool = pool or g.pool()
+        self.opt_graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.opt_graph, pool=pool):
+            gan._optimize()
             self._packed = torch.stack([losses[k] for k in gan._TRAIN_KEYS])
-        self.graphs.append(gopt)
         self.out = {k: losses[k].detach() for k in gan._TRAIN_KEYS}
 
-        gan._static_codes = None  # eager steps draw for themselves again
-        if saved is not None:
-            with torch.no_grad():
-                for n, (p, m, v, t) in saved.items():
-                    gan.groups[n].flat_param.copy_(p)
-                    gan.optimizers[n].m.copy_(m)
-                    gan.optimizers[n].v.copy_(v)
-                    gan.optimizers[n].t = t
-                for n, e in saved_ema.items():
-                    gan.optimizers[n].ema.copy_(e)
-                for p, state in zip(gan.pools or (), saved_pools):
-                    p.load_state_dict(state)
-                gan._refresh_shadows()
-
-    def __call__(self, x=None, y=None) -> Dict[str, torch.Tensor]:
+    def _replay(self):
         gan = self.gan
-        if x is not None:
-            self.sx.copy_(gan._cast(x))
-            self.sy.copy_(gan._cast(y))
-        for opt in gan.optimizers.values():
-            opt.advance_lr()
-        if self.codes is not None:
-            gan.refresh_pool_codes(self.codes)
-        for i, name in enumerate(self.names):
-            self.graphs[i].replay()
+        for name, g in self.grad_graphs.items():
+            g.replay()
             gan.sync.launch(gan.groups[name].flat_grad)
         gan.sync.wait_all()
-        self.graphs[4].replay()
-        for g in gan.groups.values():
-            g.bump_versions()
-        return self.out
+        self.opt_graph.replay()
 
-    def call_cloned(self, x, y) -> Dict[str, torch.Tensor]:
-        self(x, y)
-        p = self._packed.clone()
-        return {k: p[i] for i, k in enumerate(self.gan._TRAIN_KEYS)}

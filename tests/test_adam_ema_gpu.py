@@ -192,14 +192,24 @@ def _ctx():
     return DistContext(device=torch.device("cuda", 0))
 
 
-def test_captured_step_follows_schedule_and_averages(tmp_path):
-    from cyclegan_amd.trainer import CycleGAN, GraphedStep
+STEP_CLASSES = ["GraphedStep", "SegmentedGraphedStep"]
+
+
+def _step_class(name):
+    from cyclegan_amd import trainer
+    return getattr(trainer, name)
+
+
+@pytest.mark.parametrize("step_class", STEP_CLASSES)
+def test_captured_step_follows_schedule_and_averages(tmp_path, step_class):
+    from cyclegan_amd.trainer import CycleGAN
     d = 0.9
     data = _data(3, 7)
     torch.manual_seed(1)
     gan = CycleGAN(make_args(tmp_path, d), _ctx())
     assert gan.optimizers["X"].ema is None and gan.optimizers["Y"].ema is None
-    step = GraphedStep(gan, *data[0], warmup=1, preserve_state=True)
+    step = _step_class(step_class)(gan, *data[0], warmup=1,
+                                   preserve_state=True)
     start = {n: gan.groups[n].flat_param.clone() for n in "GFXY"}
     snaps = {n: [start[n]] for n in "GF"}
     emas = {n: [gan.optimizers[n].ema.clone()] for n in "GF"}
@@ -235,8 +245,9 @@ def test_captured_step_follows_schedule_and_averages(tmp_path):
         assert not torch.equal(emas[n][2], snaps[n][2])
 
 
-def test_capture_does_not_leak_into_state(tmp_path):
-    from cyclegan_amd.trainer import CycleGAN, GraphedStep
+@pytest.mark.parametrize("step_class", STEP_CLASSES)
+def test_capture_does_not_leak_into_state(tmp_path, step_class):
+    from cyclegan_amd.trainer import CycleGAN
     data = _data(2, 5)
     torch.manual_seed(0)
     gan = CycleGAN(make_args(tmp_path, 0.9), _ctx())
@@ -253,7 +264,7 @@ def test_capture_does_not_leak_into_state(tmp_path):
 
     s0 = state()
     assert not torch.equal(s0["G"][4], s0["G"][0])
-    GraphedStep(gan, *data[1], warmup=2, preserve_state=True)
+    _step_class(step_class)(gan, *data[1], warmup=2, preserve_state=True)
     torch.cuda.synchronize()
     s1 = state()
     for n in "GFXY":

@@ -156,13 +156,22 @@ def _data(n, seed):
             for _ in range(n)]
 
 
-def test_graphed_step_matches_eager_with_pool(tmp_path):
+STEP_CLASSES = ["GraphedStep", "SegmentedGraphedStep"]
+
+
+def _step_class(name):
+    from cyclegan_amd import trainer
+    return getattr(trainer, name)
+
+
+@pytest.mark.parametrize("step_class", STEP_CLASSES)
+def test_graphed_step_matches_eager_with_pool(tmp_path, step_class):
     """tests/test_train_gpu.py::test_graphed_step_matches_eager with the
     pool on: 6 logical steps at pool_size 3, batch 2 (fill, the fill/steady
     boundary inside step 2, swaps), eager vs 2 eager + 4 graph replays that
-    take their decisions from a planned device table."""
+    take their decisions from a planned device table. Both graph steps."""
     from cyclegan_amd.parallel import DistContext
-    from cyclegan_amd.trainer import CycleGAN, GraphedStep
+    from cyclegan_amd.trainer import CycleGAN
     ctx = DistContext(device=torch.device("cuda", 0))
     data = _data(6, 11)
 
@@ -176,10 +185,13 @@ def test_graphed_step_matches_eager_with_pool(tmp_path):
     gan_g = CycleGAN(make_args(tmp_path, pool_size=3), ctx)
     for x, y in data[:2]:
         gan_g.train_step(x, y)
-    step = GraphedStep(gan_g, *data[2], warmup=0)
+    step = _step_class(step_class)(gan_g, *data[2], warmup=0)
     gan_g.plan_pools([2] * 4, (64, 64, 3))
+    # as tests/test_train_gpu.py reads them: the static outputs of the
+    # one-graph step, the cloned ones of the segmented step
+    call = step if step_class == "GraphedStep" else step.call_cloned
     for x, y in data[2:]:
-        r_g = step(x, y)
+        r_g = call(x, y)
     torch.cuda.synchronize()
 
     assert all(o.t == 6 for o in gan_g.optimizers.values())
@@ -196,9 +208,10 @@ def test_graphed_step_matches_eager_with_pool(tmp_path):
         assert p_e.draw(8) == p_g.draw(8)
 
 
-def test_capture_preserves_pool_state(tmp_path):
+@pytest.mark.parametrize("step_class", STEP_CLASSES)
+def test_capture_preserves_pool_state(tmp_path, step_class):
     from cyclegan_amd.parallel import DistContext
-    from cyclegan_amd.trainer import CycleGAN, GraphedStep
+    from cyclegan_amd.trainer import CycleGAN
     ctx = DistContext(device=torch.device("cuda", 0))
     data = _data(2, 5)
     torch.manual_seed(0)
@@ -209,7 +222,7 @@ def test_capture_preserves_pool_state(tmp_path):
     states = [p.decision_state() for p in gan.pools]
     params = gan.groups["X"].flat_param.clone()
 
-    GraphedStep(gan, *data[1], preserve_state=True)
+    _step_class(step_class)(gan, *data[1], preserve_state=True)
     torch.cuda.synchronize()
 
     assert torch.equal(gan.groups["X"].flat_param, params)
