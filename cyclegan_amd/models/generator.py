@@ -9,20 +9,34 @@ reflect-pad(3) -> conv7x7(64) valid no-bias -> IN -> ReLU
 -> reflect-pad(3) -> conv7x7(3) valid bias glorot-init -> tanh
 
 11,383,427 parameters (verified by tests/test_models.py).
+
+``upsample="resize"`` replaces each convT3x3 s2 by nearest-2x upsampling +
+conv3x3 'same' (zero pad) — against the transpose conv's checkerboard
+artifacts; same parameters, not interchangeable weights.
 """
 
 from __future__ import annotations
 
 import torch.nn as nn
 
-from .layers import ConvNHWC, ConvTransposeNHWC, InstanceNormNHWC, ResBlock
+from .layers import (ConvNHWC, ConvTransposeNHWC, InstanceNormNHWC, ResBlock,
+                     UpsampleConvNHWC)
+
+# the two upsampling blocks: the reference's stride-2 3x3 transpose conv,
+# or nearest-2x upsampling + 3x3 conv (resize-convolution, Odena et al.
+# 2016; not in the reference). Same parameter names, shapes and count.
+UPSAMPLE_MODES = ("transpose", "resize")
 
 
 class Generator(nn.Module):
     def __init__(self, in_channels: int = 3, filters: int = 64,
                  num_downsampling_blocks: int = 2, num_residual_blocks: int = 9,
-                 num_upsample_blocks: int = 2):
+                 num_upsample_blocks: int = 2, upsample: str = "transpose"):
         super().__init__()
+        if upsample not in UPSAMPLE_MODES:
+            raise ValueError(f"upsample must be one of {UPSAMPLE_MODES}, "
+                             f"got {upsample!r}")
+        self.upsample = upsample
         f = filters
         self.stem_conv = ConvNHWC(in_channels, f, 7, 1,
                                   padding=(3, 3, 3, 3), pad_mode="reflect")
@@ -39,8 +53,9 @@ class Generator(nn.Module):
 
         ups = []
         for _ in range(num_upsample_blocks):
-            ups += [ConvTransposeNHWC(f, f // 2, 3, 2),
-                    InstanceNormNHWC(f // 2, act="relu")]
+            up = (UpsampleConvNHWC(f, f // 2) if upsample == "resize"
+                  else ConvTransposeNHWC(f, f // 2, 3, 2))
+            ups += [up, InstanceNormNHWC(f // 2, act="relu")]
             f //= 2
         self.ups = nn.ModuleList(ups)
 

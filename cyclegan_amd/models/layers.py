@@ -78,6 +78,26 @@ class ConvTransposeNHWC(nn.Module):
                                     self.act)
 
 
+class UpsampleConvNHWC(nn.Module):
+    """Resize-convolution: nearest 2x upsample, then a zero-padded 3x3
+    conv (out = 2 * in). The weight is the 3x3 OHWI master; the HIP path
+    runs the equivalent folded 4x4 transpose conv (ops.upsample_conv2d)."""
+
+    def __init__(self, cin: int, cout: int, bias: bool = False,
+                 act: Optional[str] = None, init: str = "normal002"):
+        super().__init__()
+        self.act = act
+        self.weight = nn.Parameter(torch.empty(cout, 3, 3, cin))
+        init_conv_weight_(self.weight, init)
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(cout))
+        else:
+            self.register_parameter("bias", None)
+
+    def forward(self, x):
+        return ops.upsample_conv2d(x, self.weight, self.bias, self.act)
+
+
 class InstanceNormNHWC(nn.Module):
     """tfa-style InstanceNorm: eps=1e-3, gamma~N(0,0.02), beta=0, with
     optionally fused activation and residual add."""

@@ -10,13 +10,14 @@ to explicit MI355X ops:
 - K13    loss elementwise     -> ops.losses.MAE/MSE/MSE_const
 - K14    Adam                 -> ops.adam.FusedAdam
 
-Beyond the reference: ops.augment (K15 input augmentation) and ops.pool
-(the CycleGAN image history pool).
+Beyond the reference: ops.augment (K15 input augmentation), ops.pool
+(the CycleGAN image history pool) and ops.conv.upsample_conv2d
+(resize-convolution upsampling, folded into the transpose-conv kernel).
 """
 
 from . import backend  # noqa: F401
-from .conv import (conv2d, conv_transpose2d, same_pads, set_fp8_mode,  # noqa: F401
-                   fp8_mode, Fp8Consumer)
+from .conv import (conv2d, conv_transpose2d, upsample_conv2d, same_pads,  # noqa: F401
+                   set_fp8_mode, fp8_mode, Fp8Consumer)
 from .norm import instance_norm  # noqa: F401
 from .pad import reflection_pad2d  # noqa: F401
 from .losses import MAE, MSE, MSE_const, BCE  # noqa: F401

@@ -73,6 +73,8 @@ void adam_ema_step(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
 void adam_ema_step_dev(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                        at::Tensor, at::Tensor, double, double, double, double);
 void shadow_gather(at::Tensor, at::Tensor, at::Tensor);
+void shadow_fold(at::Tensor, at::Tensor, at::Tensor);
+void fold_upconv_dw_into(at::Tensor, at::Tensor, bool, bool);
 void adam_step(at::Tensor, at::Tensor, at::Tensor, at::Tensor, double, double,
                double, double, int64_t);
 at::Tensor augment_batch(at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
@@ -139,6 +141,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_ema_step", &cyg::adam_ema_step);
   m.def("adam_ema_step_dev", &cyg::adam_ema_step_dev);
   m.def("shadow_gather", &cyg::shadow_gather);
+  // resize-convolution: folded 4x4 forms from the 3x3 masters, and the
+  // 4x4 weight gradient unfolded onto the 3x3 master's gradient block
+  m.def("shadow_fold", &cyg::shadow_fold);
+  m.def("fold_upconv_dw_into", &cyg::fold_upconv_dw_into, py::arg("dv"),
+        py::arg("out"), py::arg("accumulate"), py::arg("transposed"));
   m.def("augment_batch", &cyg::augment_batch);
   m.def("pool_exchange", &cyg::pool_exchange);
 }

@@ -10,6 +10,12 @@ Here each form is a view into one bf16 arena filled by shadow_gather
 (shadow.hip) from a precomputed int32 index map; -1 entries produce the
 alignment-pad zeros. The refresh is captured inside the hip-graph step.
 
+Resize-convolution layers (UpsampleConvNHWC) need forms that are SUMS of
+masters — the 4x4 transpose-conv kernel folded from the 3x3 one. Those
+live in a second segment (fold_buf) with an [n,4] index table, filled by
+shadow_fold right after the gather; a model without such layers has an
+empty segment and launches only the gather.
+
 GPU-only: CPU paths keep the version-keyed caches in ops.shadow (fp32
 compute needs no casting there).
 """
@@ -31,6 +37,38 @@ def _conv_like(m: torch.nn.Module) -> bool:
 
 def _convt_like(m: torch.nn.Module) -> bool:
     return type(m).__name__ == "ConvTransposeNHWC"
+
+
+def _upconv_like(m: torch.nn.Module) -> bool:
+    return type(m).__name__ == "UpsampleConvNHWC"
+
+
+# Resize-convolution fold (docs/KERNELS.md): V = M w M^T on both axes; row
+# k of M lists the 3x3 taps that 4x4 tap k sums.
+FOLD_M = ((0, 0, 1), (0, 1, 1), (1, 1, 0), (1, 0, 0))
+_FOLD_TAPS = tuple(tuple(d for d in range(3) if row[d]) for row in FOLD_M)
+
+
+def _idx_up(base: int, shape) -> torch.Tensor:
+    """Folded transpose-conv form [O,4,4,I] of a 3x3 master, as an index
+    table [O,4,4,I,4]: V[o,k,l,i] sums w[o,d,e,i] over the taps d of row k
+    and e of row l of FOLD_M, d-major, -1 where there are fewer than 4."""
+    O, KH, KW, I = shape
+    assert KH == 3 and KW == 3
+    o = torch.arange(O).view(-1, 1)
+    i = torch.arange(I).view(1, -1)
+    idx = torch.full((O, 4, 4, I, 4), -1, dtype=torch.int64)
+    for k in range(4):
+        for l in range(4):
+            terms = [(d, e) for d in _FOLD_TAPS[k] for e in _FOLD_TAPS[l]]
+            for j, (d, e) in enumerate(terms):
+                idx[:, k, l, :, j] = base + ((o * 3 + d) * 3 + e) * I + i
+    return idx.to(torch.int32)
+
+
+def _idx_up_t(base: int, shape) -> torch.Tensor:
+    """Channel-transposed folded form [I,4,4,O] (convt2d_dgrad's weight)."""
+    return _idx_up(base, shape).permute(3, 1, 2, 0, 4).contiguous()
 
 
 def _idx_p(base: int, shape) -> torch.Tensor:
@@ -116,7 +154,19 @@ class ShadowArena:
         pieces: List[torch.Tensor] = []           # int32 index chunks (cpu)
         plan: List[Tuple[torch.nn.Parameter, str, Tuple[int, ...], int]] = []
         total = 0
+        # second segment: folded forms (sums of up to 4 masters), [n,4]
+        fpieces: List[torch.Tensor] = []
+        fplan: List[Tuple[torch.nn.Parameter, str, Tuple[int, ...], int]] = []
+        ftotal = 0
         for m in module.modules():
+            if _upconv_like(m):
+                w = m.weight
+                for name, fn in (("up", _idx_up), ("up_t", _idx_up_t)):
+                    idx = fn(off[w], tuple(w.shape))
+                    fpieces.append(idx.reshape(-1, 4))
+                    fplan.append((w, name, tuple(idx.shape[:-1]), ftotal))
+                    ftotal += idx.numel() // 4
+                continue
             if _conv_like(m):
                 forms = (("p", _idx_p), ("tp", _idx_tp))
             elif _convt_like(m):
@@ -153,19 +203,34 @@ class ShadowArena:
             torch.empty(0, dtype=torch.int32, device=dev)
         self.buf = torch.empty(self.idx.numel(), dtype=torch.bfloat16, device=dev)
 
+        fpad = (-ftotal) % 8
+        if fpad:
+            fpieces.append(torch.full((fpad, 4), -1, dtype=torch.int32))
+        self.fold_idx = torch.cat(fpieces).to(dev) if fpieces else \
+            torch.empty((0, 4), dtype=torch.int32, device=dev)
+        self.fold_buf = torch.empty(self.fold_idx.shape[0],
+                                    dtype=torch.bfloat16, device=dev)
+
         # per-(master, form) shaped views into the arena
         self.views: Dict[Tuple[int, str], torch.Tensor] = {}
         self._by_param: Dict[torch.Tensor, Dict[str, torch.Tensor]] = {}
         for p, name, shape, start in plan:
             v = self.buf[start:start + int(torch.tensor(shape).prod())].view(shape)
             self._by_param.setdefault(p, {})[name] = v
+        for p, name, shape, start in fplan:
+            v = self.fold_buf[start:start + int(torch.tensor(shape).prod())]
+            self._by_param.setdefault(p, {})[name] = v.view(shape)
 
         self.refresh()
 
     def refresh(self):
-        """One gather kernel: flat fp32 masters -> every bf16 form."""
+        """One gather kernel: flat fp32 masters -> every bf16 form; one
+        fold kernel more when the model has resize-convolution layers."""
         if self.idx.numel():
             backend.ext().shadow_gather(self.group.flat_param, self.idx, self.buf)
+        if self.fold_idx.numel():
+            backend.ext().shadow_fold(self.group.flat_param, self.fold_idx,
+                                      self.fold_buf)
 
     def forms_of(self, p: torch.Tensor):
         return self._by_param.get(p)

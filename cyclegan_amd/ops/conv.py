@@ -36,7 +36,8 @@ import torch.nn.functional as F
 from . import backend, grad_sink
 from .shadow import (compute_weight, compute_weight_t, compute_weight_p,
                      compute_weight_tp, compute_bias_p, compute_weight_packp,
-                     compute_bias_packb, fp8_weight_shadow)
+                     compute_bias_packb, compute_weight_up,
+                     compute_weight_up_t, fp8_weight_shadow)
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 
@@ -478,6 +479,66 @@ class _ConvTFn(torch.autograd.Function):
         return dx, dw, db, None, None, None, None, None, None, None
 
 
+class _UpConvFn(torch.autograd.Function):
+    """Resize-convolution (nearest-2x upsample + zero-padded 3x3 conv) as
+    the 4x4 stride-2 'SAME' transpose conv with the folded kernel
+    V = M w M^T (ops.shadow.compute_weight_up): _ConvTFn with K = 4,
+    pt = pl = 1, whose 4x4 weight gradient is folded back onto the 3x3
+    master by fold_upconv_dw_into. The upsampled tensor never exists."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, act, slope):
+        ext = backend.ext()
+        x = x.contiguous()
+        out_h, out_w = 2 * x.shape[1], 2 * x.shape[2]
+        wc = compute_weight_up(w, x)
+        bc = compute_weight(bias, x) if bias is not None else None
+        slabs = ()
+        if _want_stats(bias, act):
+            y, *slabs = ext.convt2d_fwd_stats(x, wc, bc, 2, 1, 1, out_h,
+                                              out_w, act, slope)
+        else:
+            y = ext.convt2d_fwd(x, wc, bc, 2, 1, 1, out_h, out_w, act, slope)
+        ctx.save_for_backward(x, w, y)
+        ctx.conf = (act, slope, bias is not None)
+        if slabs:
+            # no zero-filled grads for the slab outputs in backward
+            ctx.set_materialize_grads(False)
+            ctx.mark_non_differentiable(*slabs)
+            return (y, *slabs)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy, *_):
+        if dy is None:  # only with set_materialize_grads(False): y unused
+            return (None,) * 5
+        x, w, y = ctx.saved_tensors
+        act, slope, has_bias = ctx.conf
+        ext = backend.ext()
+        sink = grad_sink.current()
+        dy = dy.contiguous()
+        if act != ACT_NONE:
+            dy = ext.act_bwd(dy, y, act, slope)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            wt = compute_weight_up_t(w, x)
+            dx = ext.convt2d_dgrad(dy, wt, x.shape[1], x.shape[2], 2, 1, 1)
+        if ctx.needs_input_grad[1] and not grad_sink.frozen(sink, w):
+            # dV by the role-swapped wgrad, [Cin,4,4,Cout]; the fold
+            # transposes it back while it sums the taps
+            dv = ext.conv2d_wgrad(dy, x, 4, 4, 2, 1, 1, False)
+            if sink is not None and sink.has(w):
+                out, acc = sink.take(w)
+                ext.fold_upconv_dw_into(dv, out, acc, True)
+            else:
+                dw = torch.empty(w.shape, dtype=torch.float32,
+                                 device=dv.device)
+                ext.fold_upconv_dw_into(dv, dw, False, True)
+        if has_bias and ctx.needs_input_grad[2]:
+            db = dy.float().sum(dim=(0, 1, 2))
+        return dx, dw, db, None, None
+
+
 def conv2d(
     x: torch.Tensor,
     w: torch.Tensor,
@@ -538,4 +599,31 @@ def conv_transpose2d(
     wc = w if w.dtype == x.dtype else w.to(x.dtype)
     bc = bias if (bias is None or bias.dtype == x.dtype) else bias.to(x.dtype)
     y = _convt_ref(x, wc, bc, stride, pt, pl, out_h, out_w)
+    return _apply_act(y, a, slope)
+
+
+def upsample_conv2d(
+    x: torch.Tensor,
+    w: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+    act: Optional[str] = None,
+    slope: float = 0.2,
+) -> torch.Tensor:
+    """Resize-convolution: nearest-neighbour 2x upsampling followed by a
+    zero-padded ('SAME') 3x3 stride-1 conv, [B,H,W,Cin] -> [B,2H,2W,Cout];
+    ``w`` is the OHWI 3x3 master.
+
+    On the HIP path this runs as the equivalent 4x4 stride-2 transpose
+    conv with the folded kernel (_UpConvFn). The torch path is the naive
+    formulation, and the oracle of the other.
+    """
+    assert w.shape[1] == 3 and w.shape[2] == 3, \
+        "upsample_conv2d: 3x3 kernels only"
+    a = _ACT[act]
+    if backend.use_hip(x, w) and x.dtype == torch.bfloat16:
+        return _attach_slabs(_UpConvFn.apply(x, w, bias, a, slope))
+    wc = w if w.dtype == x.dtype else w.to(x.dtype)
+    bc = bias if (bias is None or bias.dtype == x.dtype) else bias.to(x.dtype)
+    xu = F.interpolate(x.permute(0, 3, 1, 2), scale_factor=2, mode="nearest")
+    y = _conv_ref(xu.permute(0, 2, 3, 1), wc, bc, 1, (1, 1, 1, 1), "zeros")
     return _apply_act(y, a, slope)

@@ -191,6 +191,53 @@ def compute_bias_packb(b: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
     return bp
 
 
+def _fold_up_weight_torch(w: torch.Tensor) -> torch.Tensor:
+    """Resize-convolution fold V = M w M^T of a 3x3 OHWI master, [O,4,4,I]
+    in fp32 (docs/KERNELS.md) — the einsum 'kd,odei,le->okli' with M,
+    written as its at most four terms per tap added in fp32 in the arena's
+    order (d-major), so that it is the same number bit for bit."""
+    from .arena import FOLD_M
+    O, KH, KW, I = w.shape
+    assert KH == 3 and KW == 3, "upsample_conv2d: 3x3 kernels only"
+    wf = w.float()
+    v = wf.new_zeros(O, 4, 4, I)
+    for k in range(4):
+        for l in range(4):
+            for d in range(3):
+                for e in range(3):
+                    if FOLD_M[k][d] and FOLD_M[l][e]:
+                        v[:, k, l, :] += wf[:, d, e, :]
+    return v
+
+
+_cache_up: "WeakTensorKeyDictionary" = WeakTensorKeyDictionary()
+
+
+def _folded(w: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """(up, up_t) built in torch, cached per master version — fallback for
+    masters without an arena (tests, ops called directly)."""
+    ent = _cache_up.get(w)
+    key = (w._version, like.dtype)
+    if ent is not None and ent[0] == key:
+        return ent[1]
+    up = _fold_up_weight_torch(w.detach()).to(like.dtype).contiguous()
+    forms = (up, up.permute(3, 1, 2, 0).contiguous())
+    _cache_up[w] = (key, forms)
+    return forms
+
+
+def compute_weight_up(w: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """Folded 4x4 transpose-conv form [O,4,4,I] of a 3x3 master."""
+    v = _arena(w, "up", like)
+    return v if v is not None else _folded(w, like)[0]
+
+
+def compute_weight_up_t(w: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """Its channel transpose [I,4,4,O], convt2d_dgrad's operand."""
+    v = _arena(w, "up_t", like)
+    return v if v is not None else _folded(w, like)[1]
+
+
 def fp8_weight_shadow(w: torch.Tensor):
     """(wq uint8 e4m3 padded OHWI, sw fp32 scale tensor), cached per master
     version. scale = 448/amax (OCP e4m3 max normal)."""

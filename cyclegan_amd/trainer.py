@@ -77,8 +77,13 @@ class CycleGAN:
         self.checkpoint_path = os.path.join(self.checkpoint_dir, "checkpoint.pt")
 
         nrb = getattr(args, "num_residual_blocks", 9)
-        self.G = Generator(num_residual_blocks=nrb).to(self.device)
-        self.F = Generator(num_residual_blocks=nrb).to(self.device)
+        # generator upsampling blocks: "transpose" (the reference) or
+        # "resize" (nearest-2x + conv3x3); recorded in the checkpoint
+        self.upsample = getattr(args, "upsample", None) or "transpose"
+        self.G = Generator(num_residual_blocks=nrb,
+                           upsample=self.upsample).to(self.device)
+        self.F = Generator(num_residual_blocks=nrb,
+                           upsample=self.upsample).to(self.device)
         self.X = Discriminator().to(self.device)
         self.Y = Discriminator().to(self.device)
 
@@ -495,6 +500,11 @@ class CycleGAN:
     def save_checkpoint(self):
         if self.ctx.is_main:
             state = {n: getattr(self, n).state_dict() for n in self._NAMES}
+            # the generator variants share keys and shapes: say which. The
+            # default writes nothing (a missing entry means transpose), so
+            # its checkpoints keep exactly the keys they always had
+            if self.upsample != "transpose":
+                state["arch"] = {"upsample": self.upsample}
             for n in self._NAMES:
                 state[f"{n}_optimizer"] = self.optimizers[n].state_dict()
             if self.ema_decay:
@@ -514,6 +524,14 @@ class CycleGAN:
             return False
         state = torch.load(self.checkpoint_path, map_location=self.device,
                            weights_only=True)
+        # a checkpoint from before the flag has no entry: transpose
+        saved = state.get("arch", {}).get("upsample", "transpose")
+        if saved != self.upsample:
+            raise RuntimeError(
+                f"{self.checkpoint_path} was trained with --upsample {saved}, "
+                f"this run has --upsample {self.upsample}: the weights have "
+                "the same shapes but are not interchangeable; pass "
+                f"--upsample {saved} or use another --output_dir")
         for name in self._NAMES:
             getattr(self, name).load_state_dict(state[name])
         for name in self._NAMES:

@@ -19,7 +19,11 @@ N = epochs/2), stepping once per epoch; a resumed run picks the schedule
 up at the epoch the optimizer's step count implies. --ema_decay D keeps an
 exponential moving average of the generator weights inside the fused Adam
 kernel; the test epoch, the cycle plots and ``translate.py --ema`` then use
-the averaged generators.
+the averaged generators. --upsample resize builds both generators with
+resize-convolution upsampling blocks (nearest-2x + conv3x3, run as one
+folded 4x4 transpose conv) instead of the reference's transpose convs; the
+checkpoint records it: resuming with the other setting is refused, and
+``translate.py`` builds the matching generator from the checkpoint alone.
 """
 
 from __future__ import annotations
@@ -213,6 +217,13 @@ def build_parser() -> argparse.ArgumentParser:
                         help="keep an exponential moving average of the "
                              "generator weights with this decay (e.g. 0.999) "
                              "and evaluate with it; 0: off")
+    parser.add_argument("--upsample", default="transpose",
+                        choices=["transpose", "resize"],
+                        help="generator upsampling blocks. transpose: the "
+                             "reference's stride-2 3x3 transpose conv; "
+                             "resize: nearest-2x upsampling + 3x3 conv "
+                             "(no checkerboard artifacts; not in the "
+                             "reference). Recorded in the checkpoint")
     parser.add_argument("--augment", default="frozen", choices=["frozen", "epoch"],
                         help="frozen: one augmentation per sample for the run "
                              "(the reference's .map().cache()); epoch: re-drawn "

@@ -7,7 +7,8 @@ Loads G (x->y) or F (y->x) from a framework checkpoint and writes
 translated PNGs. Accepts an image folder or, with --synthetic N, random
 inputs (useful without data). Runs the same HIP kernel path as training.
 --ema translates with the averaged generator weights that a run trained
-with ``main.py --ema_decay D`` saves beside the live ones.
+with ``main.py --ema_decay D`` saves beside the live ones. The generator's
+upsampling variant (``main.py --upsample``) is read from the checkpoint.
 """
 
 from __future__ import annotations
@@ -39,8 +40,11 @@ def main():
     device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
     dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
 
-    gen = Generator(num_residual_blocks=args.num_residual_blocks).to(device)
     state = torch.load(args.checkpoint, map_location=device, weights_only=True)
+    # the upsampling variant is the checkpoint's (none recorded: transpose)
+    upsample = state.get("arch", {}).get("upsample", "transpose")
+    gen = Generator(num_residual_blocks=args.num_residual_blocks,
+                    upsample=upsample).to(device)
     key = "G" if args.direction == "x2y" else "F"
     if args.ema:
         key += "_ema"
