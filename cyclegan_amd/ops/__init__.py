@@ -11,8 +11,9 @@ to explicit MI355X ops:
 - K14    Adam                 -> ops.adam.FusedAdam
 
 Beyond the reference: ops.augment (K15 input augmentation), ops.pool
-(the CycleGAN image history pool) and ops.conv.upsample_conv2d
-(resize-convolution upsampling, folded into the transpose-conv kernel).
+(the CycleGAN image history pool), ops.conv.upsample_conv2d
+(resize-convolution upsampling, folded into the transpose-conv kernel)
+and ops.ssim.SSIM (per-sample structural similarity with a backward).
 """
 
 from . import backend  # noqa: F401
@@ -22,3 +23,4 @@ from .norm import instance_norm  # noqa: F401
 from .pad import reflection_pad2d  # noqa: F401
 from .losses import MAE, MSE, MSE_const, BCE  # noqa: F401
 from .pool import pool_exchange, ImagePool  # noqa: F401
+from .ssim import SSIM  # noqa: F401

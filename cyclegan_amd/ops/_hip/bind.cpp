@@ -80,6 +80,9 @@ void adam_step(at::Tensor, at::Tensor, at::Tensor, at::Tensor, double, double,
 at::Tensor augment_batch(at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
                          at::Tensor);
 at::Tensor pool_exchange(at::Tensor, at::Tensor, at::Tensor, at::Tensor);
+std::vector<at::Tensor> ssim_fwd(at::Tensor, at::Tensor, int64_t);
+at::Tensor ssim_bwd(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                    at::Tensor);
 }  // namespace cyg
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -148,4 +151,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("accumulate"), py::arg("transposed"));
   m.def("augment_batch", &cyg::augment_batch);
   m.def("pool_exchange", &cyg::pool_exchange);
+  // per-sample mean SSIM: [out] or, save_maps 1/2, [out, ay, b, c(, ax)]
+  m.def("ssim_fwd", &cyg::ssim_fwd, py::arg("y_true"), py::arg("y_pred"),
+        py::arg("save_maps") = 0);
+  m.def("ssim_bwd", &cyg::ssim_bwd, py::arg("x"), py::arg("y"), py::arg("am"),
+        py::arg("bm"), py::arg("cm"), py::arg("dout"));
 }

@@ -23,7 +23,10 @@ on the MI355X execution model:
 - compute dtype bf16 on GPU (fp32 masters), fp32 on CPU;
 - optional image history pool (``pool_size`` > 0, ops/pool.py; not in the
   reference): the discriminator losses see fakes exchanged with a buffer
-  of earlier ones, the generator losses keep the fresh fakes.
+  of earlier ones, the generator losses keep the fresh fakes;
+- optional SSIM term in the cycle loss (``cycle_ssim`` = W in (0, 1],
+  ops/ssim.py; not in the reference): per sample (1-W)·MAE + W·(1-SSIM),
+  and two SSIM metrics in the test epoch (``test_ssim``, implied by W > 0).
 """
 
 from __future__ import annotations
@@ -35,7 +38,7 @@ from typing import Dict, Optional
 import torch
 
 from .models import Generator, Discriminator
-from .ops import MAE, MSE, MSE_const, ImagePool, backend, grad_sink
+from .ops import MAE, MSE, MSE_const, SSIM, ImagePool, backend, grad_sink
 from .ops.adam import FusedAdam
 from .parallel import DistContext, GradSync, FlatParamGroup
 
@@ -126,6 +129,17 @@ class CycleGAN:
         # while a graph step warms up and captures: its static all-pass
         # codes, so train_step draws nothing
         self._static_codes = None
+
+        # SSIM: weight of the (1 - SSIM) term in the cycle loss, and the two
+        # SSIM metrics of the test epoch (always on with the loss term).
+        # Neither touches the weights: checkpoints are interchangeable
+        self.cycle_ssim = float(getattr(args, "cycle_ssim", 0.0) or 0.0)
+        if not 0.0 <= self.cycle_ssim <= 1.0:
+            raise ValueError("cycle_ssim must be in [0, 1]")
+        self.test_ssim = (bool(getattr(args, "test_ssim", False))
+                          or self.cycle_ssim > 0.0)
+        self._test_keys = self._TEST_KEYS + (
+            self._SSIM_KEYS if self.test_ssim else ())
 
         # lazily-captured hip-graph step (main.py at N=1)
         self.graphed = None
@@ -280,6 +294,11 @@ class CycleGAN:
         return self.reduce_mean(MSE_const(discriminate_fake, 1.0))
 
     def cycle_loss(self, real, cycled):
+        if self.cycle_ssim:
+            w = self.cycle_ssim
+            return self.LAMBDA_CYCLE * self.reduce_mean(
+                (1.0 - w) * MAE(real, cycled)
+                + w * (1.0 - SSIM(real, cycled)))
         return self.LAMBDA_CYCLE * self.reduce_mean(MAE(real, cycled))
 
     def identity_loss(self, real, same):
@@ -302,6 +321,8 @@ class CycleGAN:
     _TEST_KEYS = _TRAIN_KEYS + ("error/MAE(X, F(G(X)))",
                                 "error/MAE(Y, G(F(Y)))",
                                 "error/MAE(X, F(X))", "error/MAE(Y, G(Y))")
+    # added to an instance's test keys by test_ssim
+    _SSIM_KEYS = ("error/SSIM(X, F(G(X)))", "error/SSIM(Y, G(F(Y)))")
 
     def _zero_losses(self, keys) -> Dict[str, torch.Tensor]:
         z = torch.zeros((), device=self.device)
@@ -468,7 +489,7 @@ class CycleGAN:
     def test_step(self, x, y) -> Dict[str, torch.Tensor]:
         x, y = self._cast(x), self._cast(y)
         if x.shape[0] == 0:  # empty DP slice of a short final batch
-            return self._zero_losses(self._TEST_KEYS)
+            return self._zero_losses(self._test_keys)
         fake_x, fake_y, cycle_x, cycle_y = self.cycle_step(x, y)
 
         discriminate_fake_x = self.X(fake_x)
@@ -486,13 +507,19 @@ class CycleGAN:
         X_loss = self.discriminator_loss(self.X(x), discriminate_fake_x)
         Y_loss = self.discriminator_loss(self.Y(y), discriminate_fake_y)
 
-        return {
+        results = {
             **losses, "loss_X/loss": X_loss, "loss_Y/loss": Y_loss,
             "error/MAE(X, F(G(X)))": self.reduce_mean(MAE(x, cycle_x)),
             "error/MAE(Y, G(F(Y)))": self.reduce_mean(MAE(y, cycle_y)),
             "error/MAE(X, F(X))": self.reduce_mean(MAE(x, same_x)),
             "error/MAE(Y, G(Y))": self.reduce_mean(MAE(y, same_y)),
         }
+        if self.test_ssim:
+            results["error/SSIM(X, F(G(X)))"] = self.reduce_mean(
+                SSIM(x, cycle_x))
+            results["error/SSIM(Y, G(F(Y)))"] = self.reduce_mean(
+                SSIM(y, cycle_y))
+        return results
 
     # ---- checkpoint (reference main.py:148-170: one overwriting prefix,
     # all 4 models + 4 optimizer states, auto-resume if present) ----

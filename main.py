@@ -24,6 +24,11 @@ resize-convolution upsampling blocks (nearest-2x + conv3x3, run as one
 folded 4x4 transpose conv) instead of the reference's transpose convs; the
 checkpoint records it: resuming with the other setting is refused, and
 ``translate.py`` builds the matching generator from the checkpoint alone.
+--cycle_ssim W (0..1) mixes a structural-similarity term into the cycle
+loss, per sample (1-W)·MAE + W·(1-SSIM) with the SSIM of
+``tf.image.ssim(max_val=2)`` (ops/ssim.py); --test_ssim adds the SSIM of
+the two cycles to the test epoch's metrics (implied by --cycle_ssim > 0).
+Neither changes the checkpoint.
 """
 
 from __future__ import annotations
@@ -169,7 +174,12 @@ def main(args):
                   f'MAE(Y, G(F(Y))): {results["error/MAE(Y, G(F(Y)))"]:.04f}\n'
                   f'MAE(X, F(X)): {results["error/MAE(X, F(X))"]:.04f}\t\t'
                   f'MAE(Y, G(Y)): {results["error/MAE(Y, G(Y))"]:.04f}\n'
-                  f'Elapse: {end - start:.02f}s\n')
+                  + (f'SSIM(X, F(G(X))): '
+                     f'{results["error/SSIM(X, F(G(X)))"]:.04f}\t\t'
+                     f'SSIM(Y, G(F(Y))): '
+                     f'{results["error/SSIM(Y, G(F(Y)))"]:.04f}\n'
+                     if gan.test_ssim else '')
+                  + f'Elapse: {end - start:.02f}s\n')
 
         if epoch % 10 == 0 or epoch == args.epochs - 1:
             gan.save_checkpoint()
@@ -224,6 +234,14 @@ def build_parser() -> argparse.ArgumentParser:
                              "resize: nearest-2x upsampling + 3x3 conv "
                              "(no checkerboard artifacts; not in the "
                              "reference). Recorded in the checkpoint")
+    parser.add_argument("--cycle_ssim", default=0.0, type=float,
+                        help="weight W in [0, 1] of a structural-similarity "
+                             "term in the cycle loss: per sample "
+                             "(1-W)*MAE + W*(1-SSIM); 0: the reference's "
+                             "pure L1 (not in the reference)")
+    parser.add_argument("--test_ssim", action="store_true",
+                        help="also report the SSIM of both cycles in the "
+                             "test epoch (implied by --cycle_ssim > 0)")
     parser.add_argument("--augment", default="frozen", choices=["frozen", "epoch"],
                         help="frozen: one augmentation per sample for the run "
                              "(the reference's .map().cache()); epoch: re-drawn "
@@ -242,6 +260,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("--lr_decay_epochs must be in [0, --epochs]")
     if not 0.0 <= args.ema_decay < 1.0:
         parser.error("--ema_decay must be in [0, 1)")
+    if not 0.0 <= args.cycle_ssim <= 1.0:
+        parser.error("--cycle_ssim must be in [0, 1]")
+    if args.cycle_ssim > 0.0:
+        args.test_ssim = True
     return args
 
 
