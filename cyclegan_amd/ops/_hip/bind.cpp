@@ -18,6 +18,9 @@ std::vector<at::Tensor> convt2d_fwd_stats(at::Tensor, at::Tensor,
                                           int64_t, double);
 at::Tensor conv2d_dgrad(at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
                         int64_t, int64_t, int64_t, int64_t, bool);
+at::Tensor reflect_dgrad_rowmap(int64_t, int64_t, int64_t, int64_t, int64_t,
+                                int64_t, int64_t, int64_t, int64_t, bool,
+                                bool);
 at::Tensor convt2d_dgrad(at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
                          int64_t, int64_t);
 at::Tensor conv2d_wgrad(at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
@@ -91,6 +94,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd_stats", &cyg::conv2d_fwd_stats);
   m.def("convt2d_fwd_stats", &cyg::convt2d_fwd_stats);
   m.def("conv2d_dgrad", &cyg::conv2d_dgrad);
+  // row order of the direct-fold reflect dgrad as a table (host only)
+  m.def("reflect_dgrad_rowmap", &cyg::reflect_dgrad_rowmap, py::arg("B"),
+        py::arg("H"), py::arg("W"), py::arg("pt"), py::arg("pb"),
+        py::arg("pl"), py::arg("pr"), py::arg("KH"), py::arg("KW"),
+        py::arg("trim") = true, py::arg("frame") = false);
   m.def("convt2d_dgrad", &cyg::convt2d_dgrad);
   m.def("conv2d_wgrad", &cyg::conv2d_wgrad);
   // the reduce writes the parameter's true OHWI gradient block `out`

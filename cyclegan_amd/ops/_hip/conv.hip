@@ -11,7 +11,9 @@
 // Kernels in this file:
 //   conv_glds_kernel     production conv/convT: LDS-DMA staging, n-tile
 //                        16/64/128 (conv_ntile), PHASED form for the
-//                        stride-2 convT; optional InstanceNorm slab epilogue
+//                        stride-2 convT, RING form for the reflect dgrad
+//                        (window tiles first, tap-trimmed ring tiles
+//                        last); optional InstanceNorm slab epilogue
 //   conv_gemm_kernel     fallback for Cin % 8 != 0 or tensors past 2 GiB
 //   conv_fp8_kernel      e4m3 forward conv (quant_fp8_kernel,
 //                        quant_fp8_d_kernel, amax_roll_kernel feed it)
@@ -51,6 +53,115 @@ constexpr int BM = 128, BN = 64, BK = 64;
 constexpr int NTHREADS = 256;
 constexpr int LDK = BK + 8;  // +16B pad: conflict-free b128 column-of-rows reads
 
+// ---------------- reflect dgrad: layout and row order ----------------
+#define HDEV __host__ __device__ __forceinline__
+
+// Compact layout of the padded-frame pixels outside the window, per
+// sample: the rows above the window, then the rows below it (both OW
+// wide), then for each window row its left and right pieces side by side.
+// Shared by the dgrad row decode and reflect_ring_add_kernel.
+HDEV int ring_index(int qh, int qw, int OH, int OW, int wt, int wl, int wH,
+                    int wW) {
+  if (qh < wt) return qh * OW + qw;
+  if (qh >= wt + wH) return (qh - wH) * OW + qw;
+  return (OH - wH) * OW + (qh - wt) * (OW - wW) + (qw < wl ? qw : qw - wW);
+}
+
+// Which GEMM row of the direct-fold reflect dgrad is which pixel of the
+// padded frame [B, pt+H+pb, pl+W+pr]. Only the enumeration lives here;
+// where a pixel is stored is ring_index's business and does not depend on
+// the order.
+//   window tiles (tile < wtiles): the B*H*W window pixels in (b,i,j)
+//     order, i.e. the forward conv's tiles; they run every tap.
+//   ring tiles, behind them: the pixels outside the window in four
+//     classes (top rows, bottom rows, left and right pieces of the window
+//     rows), each in (b,qh,qw) order and padded to whole tiles, so a tile
+//     holds one class and its rows share a tap window (reflect_taps).
+// frame = 1 (CYG_DGRAD_FRAME_ORDER=1) enumerates the padded frame row by
+// row instead: every tile is a "window" tile and there are no ring tiles.
+struct ReflectOrder {
+  int B, H, W;         // the window: the unpadded image
+  int pt, pb, pl, pr;  // ring widths
+  int KH, KW;
+  int frame;           // rows enumerate the padded frame
+  int trim;            // ring tiles walk only their class's taps
+  int wtiles;          // tiles before the first ring tile
+  int cstart[5];       // first tile of top, bottom, left, right; [4] = all
+  int crows[4];        // rows of each class, all samples together
+};
+
+// Taps of a ring class that can have a source inside dy, as the rectangle
+// [kh0,kh1) x [kw0,kw1): the source row is oh = qh - kh in [0, HP-KH+1).
+// A top row has qh < pt, so kh <= qh < pt; a bottom row qh >= HP-pb, so
+// kh > qh - (HP-KH+1) >= KH-pb-1; columns alike. cls 0 (window) and
+// untrimmed calls get every tap.
+struct TapWindow { int kh0, kh1, kw0, kw1; };
+HDEV TapWindow reflect_taps(const ReflectOrder& o, int cls) {
+  TapWindow t = {0, o.KH, 0, o.KW};
+  if (!o.trim) return t;
+  if (cls == 1) t.kh1 = o.pt < o.KH ? o.pt : o.KH;
+  if (cls == 2) t.kh0 = o.KH > o.pb ? o.KH - o.pb : 0;
+  if (cls == 3) t.kw1 = o.pl < o.KW ? o.pl : o.KW;
+  if (cls == 4) t.kw0 = o.KW > o.pr ? o.KW - o.pr : 0;
+  return t;
+}
+
+// 0 = window (or any tile of the frame order), 1..4 = top, bottom, left,
+// right. cstart is non-decreasing; an empty class has no tile.
+HDEV int reflect_tile_class(const ReflectOrder& o, int tile) {
+  if (tile < o.wtiles) return 0;
+  return 1 + (tile >= o.cstart[1]) + (tile >= o.cstart[2]) +
+         (tile >= o.cstart[3]);
+}
+
+// Row r of a tile: the padded-frame pixel (b, qh, qw), whether it is a row
+// at all (ok), its class, its tile's tap window, and dst, its pixel slot in
+// the [dx | ring] allocation (element offset = dst * channels).
+struct ReflectRow {
+  int ok, b, qh, qw, cls;
+  TapWindow taps;
+  long dst;
+};
+HDEV ReflectRow reflect_row(const ReflectOrder& o, int tile, int r) {
+  const int HP = o.pt + o.H + o.pb, WP = o.pl + o.W + o.pr;
+  ReflectRow d;
+  d.cls = reflect_tile_class(o, tile);
+  d.taps = reflect_taps(o, d.cls);
+  if (d.cls == 0) {
+    const long m = (long)tile * BM + r;
+    const int fh = o.frame ? HP : o.H, fw = o.frame ? WP : o.W;
+    d.ok = m < (long)o.B * fh * fw;
+    const long mm = d.ok ? m : 0;
+    d.qw = (int)(mm % fw) + (o.frame ? 0 : o.pl);
+    d.qh = (int)((mm / fw) % fh) + (o.frame ? 0 : o.pt);
+    d.b = (int)(mm / ((long)fw * fh));
+  } else {
+    const int c = d.cls;
+    const int start = c == 1 ? o.cstart[0] : c == 2 ? o.cstart[1]
+                    : c == 3 ? o.cstart[2] : o.cstart[3];
+    const int rows = c == 1 ? o.crows[0] : c == 2 ? o.crows[1]
+                   : c == 3 ? o.crows[2] : o.crows[3];
+    const int wide = c <= 2 ? WP : c == 3 ? o.pl : o.pr;  // row length
+    const int x = (tile - start) * BM + r;
+    d.ok = x < rows;
+    const int xx = d.ok ? x : 0;
+    const int per = rows / o.B;  // rows of one sample
+    d.b = xx / per;
+    const int rem = xx - d.b * per;
+    d.qh = rem / wide + (c == 1 ? 0 : c == 2 ? o.pt + o.H : o.pt);
+    d.qw = rem % wide + (c == 4 ? o.pl + o.W : 0);
+  }
+  const int i = d.qh - o.pt, j = d.qw - o.pl;
+  if ((unsigned)i < (unsigned)o.H && (unsigned)j < (unsigned)o.W) {
+    d.dst = ((long)d.b * o.H + i) * o.W + j;
+  } else {
+    const long rp = (long)HP * WP - (long)o.H * o.W;
+    d.dst = (long)o.B * o.H * o.W + d.b * rp +
+            ring_index(d.qh, d.qw, HP, WP, o.pt, o.pl, o.H, o.W);
+  }
+  return d;
+}
+
 struct ConvParams {
   const short* __restrict__ x;   // [B,H,W,Cin] bf16 raw
   const short* __restrict__ w;   // [Cout,KH,KW,Cin] bf16 raw
@@ -73,26 +184,13 @@ struct ConvParams {
   float* psum;
   float* psq;
   int tps;
-  // reflect dgrad straight into the unpadded frame (non-phased convT
-  // gather only; ringoff == 0 = off). The M space is still the padded
-  // frame [B,OH,OW]; rows inside the window wt <= oh < wt+wH,
-  // wl <= ow < wl+wW go to y as a [B,wH,wW,Cout] image, every other row to
-  // the compact ring image that starts ringoff elements after y
-  // (ring_index below).
-  long ringoff;
-  int wt, wl, wH, wW;
+  // reflect dgrad straight into the unpadded frame (the RING instantiation
+  // of conv_glds_kernel only): window pixels of the padded frame [B,OH,OW]
+  // go to y as a [B,H,W,Cout] image, every other pixel to the compact ring
+  // image behind it (ring_index below). ro says which GEMM row is which
+  // pixel; mtiles counts its window and ring tiles together.
+  ReflectOrder ro;
 };
-
-// Compact layout of the padded-frame pixels outside the window, per
-// sample: the rows above the window, then the rows below it (both OW
-// wide), then for each window row its left and right pieces side by side.
-// Shared by the dgrad row decode and reflect_ring_add_kernel.
-DEV int ring_index(int qh, int qw, int OH, int OW, int wt, int wl, int wH,
-                   int wW) {
-  if (qh < wt) return qh * OW + qw;
-  if (qh >= wt + wH) return (qh - wH) * OW + qw;
-  return (OH - wH) * OW + (qh - wt) * (OW - wW) + (qw < wl ? qw : qw - wW);
-}
 
 // XCD-aware block remap: hardware dispatches blockIdx round-robin over the
 // 8 XCDs, so consecutive tiles (which gather overlapping input rows) land
@@ -307,7 +405,8 @@ struct ConvSmemT {
 
 constexpr int NW = 8;  // waves per block of the glds kernels (conv, wgrad)
 
-template <bool IS_CONVT, int STRIDE, int BNT, bool PHASED = false>
+template <bool IS_CONVT, int STRIDE, int BNT, bool PHASED = false,
+          bool RING = false>
 __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
   constexpr int NT = NW * 64;        // threads
   constexpr int API = 16 / NW;       // A glds instructions per wave
@@ -329,9 +428,27 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
   // stride-2 convT-gather decode prefers the hardware round-robin (its
   // taps scatter anyway and chunking hotspots DRAM channels): measured
   // -25% on the s2 dgrad shape, +6% on the K3 forward.
-  const int bid = (IS_CONVT && STRIDE == 2)
-                      ? blockIdx.x : xcd_chunk(blockIdx.x, gridDim.x);
-  const int mt = bid % p.mtiles, nt = bid / p.mtiles;
+  int mt, nt;
+  if (RING) {
+    // RING (reflect dgrad into the unpadded frame, p.ro): the window tiles
+    // take the low block ids, chunked over the XCDs among themselves like
+    // a forward conv's; the short ring tiles take the highest ids, so they
+    // are dispatched last and fill the tail of the launch.
+    static_assert(!RING || (IS_CONVT && STRIDE == 1 && !PHASED), "RING");
+    const int nbw = p.ro.wtiles * p.ntiles;
+    const int rb = (int)blockIdx.x - nbw;
+    if (rb < 0) {
+      const int bid = xcd_chunk(blockIdx.x, nbw);
+      mt = bid % p.ro.wtiles; nt = bid / p.ro.wtiles;
+    } else {
+      const int rt = p.mtiles - p.ro.wtiles;
+      mt = p.ro.wtiles + rb % rt; nt = rb / rt;
+    }
+  } else {
+    const int bid = (IS_CONVT && STRIDE == 2)
+                        ? blockIdx.x : xcd_chunk(blockIdx.x, gridDim.x);
+    mt = bid % p.mtiles; nt = bid / p.mtiles;
+  }
   const int n0 = nt * BNT;
 
   // PHASED (convT stride-2 only): the M space is regrouped into 4 output
@@ -345,10 +462,26 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
   const long m0 = PHASED ? (long)(mt - phase * tpp) * BM : (long)mt * BM;
   const int nvh = PHASED ? ((p.KH - phh + 1) >> 1) : 0;
   const int nvw = PHASED ? ((p.KW - phw + 1) >> 1) : 0;
-  const long KEFF = PHASED ? (long)nvh * nvw * p.Cin : p.KTOT;
+  // RING: a ring tile enumerates only its class's tap rectangle
+  // (block-uniform, reflect_taps): tap counters (dkh, dkw) below run over
+  // [0,kh1-kh0) x [0,nkw), the real tap is (kh0 + dkh, kw0 + dkw). Every
+  // tap left out has no source inside dy for any row of the tile.
+  const TapWindow tw =
+      RING ? reflect_taps(p.ro, reflect_tile_class(p.ro, mt)) : TapWindow{};
+  const int nkw = RING ? tw.kw1 - tw.kw0 : 0;
+  const long KEFF = PHASED ? (long)nvh * nvw * p.Cin
+                  : RING ? (long)(tw.kh1 - tw.kh0) * nkw * p.Cin : p.KTOT;
+  const int tapw = PHASED ? nvw : RING ? nkw : p.KW;  // taps per counter row
 
   for (int r = tid; r < BM; r += NT) {
-    if (PHASED) {
+    if (RING) {
+      const ReflectRow d = reflect_row(p.ro, mt, r);
+      sm.rowok[r] = d.ok;
+      sm.rowxb[r] = (unsigned)((long)d.b * p.H * p.W * p.Cin * 2);
+      sm.rowyb[r] = d.dst * p.Cout;
+      sm.rowih[r] = d.qh + p.pt - tw.kh0;  // oh = this - dkh
+      sm.rowiw[r] = d.qw + p.pl - tw.kw0;
+    } else if (PHASED) {
       long mp = m0 + r;
       long Mp = (long)p.B * OH2 * OW2;
       bool ok = mp < Mp;
@@ -372,21 +505,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
       int b = (int)(mm / ((long)p.OW * p.OH));
       sm.rowok[r] = ok;
       sm.rowxb[r] = (unsigned)((long)b * p.H * p.W * p.Cin * 2);
-      long yb = ((long)(b * p.OH + oh) * p.OW + ow) * p.Cout;
-      if (IS_CONVT && p.ringoff != 0) {
-        // reflect dgrad: window pixels land in the unpadded image, the
-        // rest in the ring image behind it
-        const int i = oh - p.wt, j = ow - p.wl;
-        if ((unsigned)i < (unsigned)p.wH && (unsigned)j < (unsigned)p.wW) {
-          yb = (((long)b * p.wH + i) * p.wW + j) * p.Cout;
-        } else {
-          const long rp = (long)p.OH * p.OW - (long)p.wH * p.wW;
-          yb = p.ringoff +
-               (b * rp + ring_index(oh, ow, p.OH, p.OW, p.wt, p.wl, p.wH,
-                                    p.wW)) * p.Cout;
-        }
-      }
-      sm.rowyb[r] = yb;
+      sm.rowyb[r] = ((long)(b * p.OH + oh) * p.OW + ow) * p.Cout;
       if (IS_CONVT) {
         sm.rowih[r] = oh + p.pt;
         sm.rowiw[r] = ow + p.pl;
@@ -418,10 +537,17 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
   const bool bw_on = w * BPI < TBI;  // waves beyond TBI stage no B
   static_assert(BNT == 16 || BNT == 64 || BNT == 128, "BNT");
 
-  auto rx = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)p.x, 0, (unsigned)((long)p.B * p.H * p.W * p.Cin * 2), 0x00020000);
-  auto rw = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)p.w, 0, (unsigned)(p.Cout * p.KTOT * 2), 0x00020000);
+  unsigned xbytes = (unsigned)((long)p.B * p.H * p.W * p.Cin * 2);
+  unsigned wbytes = (unsigned)(p.Cout * p.KTOT * 2);
+  if (RING) {
+    // hipcc shares these products with the per-row ones of reflect_row and
+    // leaves them in VGPRs; a descriptor in VGPRs costs a readfirstlane
+    // loop around every glds
+    xbytes = __builtin_amdgcn_readfirstlane(xbytes);
+    wbytes = __builtin_amdgcn_readfirstlane(wbytes);
+  }
+  auto rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, xbytes, 0x00020000);
+  auto rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, wbytes, 0x00020000);
 
   const int nk = (int)((KEFF + BK - 1) / BK);
   const bool big_ci = p.Cin >= BK;  // wave-uniform
@@ -430,7 +556,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
   // (every Cin/64 K-steps); otherwise one predicated add per instruction.
   long kcur;
   bool kv;
-  int ci, dkh, dkw;  // PHASED: dkh/dkw hold (vh, vw)
+  int ci, dkh, dkw;  // PHASED: (vh, vw); RING: counters inside tw
   unsigned avo[API];
   bool avalid[API];
   unsigned bvo[BPI];
@@ -471,6 +597,8 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
     long kw_idx = kcur;
     if (PHASED)
       kw_idx = ((long)(2 * dkh + phh) * p.KW + (2 * dkw + phw)) * p.Cin + ci;
+    if (RING)
+      kw_idx = ((long)(tw.kh0 + dkh) * p.KW + (tw.kw0 + dkw)) * p.Cin + ci;
     #pragma unroll
     for (int j = 0; j < BPI; ++j)
       bvo[j] = (unsigned)(((long)bn[j] * p.KTOT + kw_idx) * 2);
@@ -479,13 +607,8 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
   auto decode_tap = [&]() {
     int tap = (int)(kcur / p.Cin);
     ci = (int)(kcur - (long)tap * p.Cin);
-    if (PHASED) {
-      dkh = tap / nvw;          // vh
-      dkw = tap - dkh * nvw;    // vw
-    } else {
-      dkh = tap / p.KW;
-      dkw = tap - dkh * p.KW;
-    }
+    dkh = tap / tapw;          // PHASED: vh
+    dkw = tap - dkh * tapw;    // PHASED: vw
   };
 
   auto init_state = [&]() {
@@ -505,11 +628,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(ConvParams p) {
       ci += BK;
       if (ci >= p.Cin) {
         ci -= p.Cin;
-        if (PHASED) {
-          if (++dkw == nvw) { dkw = 0; ++dkh; }
-        } else {
-          if (++dkw == p.KW) { dkw = 0; ++dkh; }
-        }
+        if (++dkw == tapw) { dkw = 0; ++dkh; }
         recompute_a();
         recompute_b();
       } else {
@@ -1769,7 +1888,7 @@ DEV int span_nth_out(Span2 s, int k) {  // k-th index outside
 
 // ---------------- reflect ring add (direct-fold dgrad) ----------------
 // The dgrad has written window pixels of the padded frame straight into
-// dx and the others into the ring image (ConvParams::ringoff). Only dx
+// dx and the others into the ring image (ReflectRow::dst). Only dx
 // pixels in a mirrored row or column (rs / cs) receive anything more; one
 // thread per 8 channels of such a pixel re-sums it in
 // reflect_fold_kernel's candidate order (rows outer, cols inner; direct,
@@ -1885,22 +2004,61 @@ static int conv_ntile(int Cout) {
   return (Cout % 128) == 0 ? 128 : 64;
 }
 
-template <bool IS_CONVT, int STRIDE, int BNT, bool PHASED = false>
+template <bool IS_CONVT, int STRIDE, int BNT, bool PHASED = false,
+          bool RING = false>
 static void launch_one_glds(const ConvParams& p, hipStream_t stream) {
   constexpr size_t SMB = sizeof(ConvSmemT<BNT>);
   static bool init = []() {
     hipFuncSetAttribute(
-        (const void*)(conv_glds_kernel<IS_CONVT, STRIDE, BNT, PHASED>),
+        (const void*)(conv_glds_kernel<IS_CONVT, STRIDE, BNT, PHASED, RING>),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMB);
     return true;
   }();
   (void)init;
-  hipLaunchKernelGGL((conv_glds_kernel<IS_CONVT, STRIDE, BNT, PHASED>),
+  hipLaunchKernelGGL((conv_glds_kernel<IS_CONVT, STRIDE, BNT, PHASED, RING>),
                      dim3((long)p.mtiles * p.ntiles), dim3(NW * 64), SMB,
                      stream, p);
   hipError_t err = hipGetLastError();
   TORCH_CHECK(err == hipSuccess, "conv_glds launch failed (BNT=", BNT,
-              " PHASED=", PHASED, "): ", hipGetErrorString(err));
+              " PHASED=", PHASED, " RING=", RING, "): ",
+              hipGetErrorString(err));
+}
+
+// Row order of the direct-fold reflect dgrad (ReflectOrder). frame: the
+// plain padded-frame enumeration; trim: ring tiles walk only their tap
+// window (the caller allows it when the gather's Cin % BK == 0, so that
+// every kept K-step is a K-step of the untrimmed walk).
+static ReflectOrder reflect_order(int B, int H, int W, int pt, int pb, int pl,
+                                  int pr, int KH, int KW, bool frame,
+                                  bool trim) {
+  ReflectOrder o{};
+  o.B = B; o.H = H; o.W = W;
+  o.pt = pt; o.pb = pb; o.pl = pl; o.pr = pr;
+  o.KH = KH; o.KW = KW;
+  o.frame = frame; o.trim = trim && !frame;
+  const long HP = H + pt + pb, WP = W + pl + pr;
+  o.wtiles = cdiv(frame ? B * HP * WP : (long)B * H * W, BM);
+  const long rows[4] = {B * pt * WP, B * pb * WP, (long)B * H * pl,
+                        (long)B * H * pr};
+  o.cstart[0] = o.wtiles;
+  for (int c = 0; c < 4; ++c) {
+    o.crows[c] = frame ? 0 : (int)rows[c];
+    o.cstart[c + 1] = o.cstart[c] + cdiv(o.crows[c], BM);
+  }
+  return o;
+}
+
+// The reflect dgrad gather: 64- or 128-wide n-tiles only (Cout <= 16 takes
+// the 64-wide tile, as in the phased launch).
+static void launch_ring(ConvParams p, hipStream_t stream) {
+  p.mtiles = p.ro.cstart[4];
+  if (conv_ntile(p.Cout) == 128) {
+    p.ntiles = cdiv(p.Cout, 128);
+    launch_one_glds<true, 1, 128, false, true>(p, stream);
+  } else {
+    p.ntiles = cdiv(p.Cout, 64);
+    launch_one_glds<true, 1, 64, false, true>(p, stream);
+  }
 }
 
 template <bool IS_CONVT, int BNT>
@@ -2151,9 +2309,16 @@ at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt, int64_t H, int64_t W,
     // image + ring are exactly the padded frame's size: dx is the leading
     // [B,H,W,C] of the same allocation, the ring image the rest
     auto dx = dxp.view({-1}).narrow(0, 0, nimg).view({B, H, W, C});
-    p.ringoff = nimg;
-    p.wt = pt; p.wl = pl; p.wH = H; p.wW = W;
-    launch_conv(p, true, stream);
+    const int KH = wt.size(1), KW = wt.size(2);
+    TORCH_CHECK(dy.size(1) == HP - KH + 1 && dy.size(2) == WP - KW + 1,
+                "reflect dgrad: dy is not the stride-1 output frame");
+    // Window tiles first, tap-trimmed ring tiles last (ReflectOrder).
+    // CYG_DGRAD_FRAME_ORDER=1, read per call, enumerates the padded frame
+    // instead and runs every tap everywhere (A/B runs, bisection).
+    p.ro = reflect_order(B, H, W, pt, pb, pl, pr, KH, KW,
+                         env_flag(getenv("CYG_DGRAD_FRAME_ORDER")),
+                         p.Cin % BK == 0);
+    launch_ring(p, stream);
     const Span2 rs = mirror_span(H, pt, pb), cs = mirror_span(W, pl, pr);
     const long nr = rs.n0 + rs.n1, nc = cs.n0 + cs.n1;
     const long total = B * (nr * W + (H - nr) * nc) * (C / 8);
@@ -2175,6 +2340,34 @@ at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt, int64_t H, int64_t W,
                      (int)dy.size(0), (int)H, (int)W, (int)wt.size(0),
                      (int)pt, (int)pb, (int)pl, (int)pr);
   return dx;
+}
+
+// The direct-fold reflect dgrad's row order as a CPU int32 table, one line
+// [ok, b, qh, qw, cls, kh0, kh1, kw0, kw1, dst] per (tile, r), tiles in
+// order: reflect_row, the function the kernel's prologue calls, run on the
+// host. Launches nothing and needs no GPU.
+at::Tensor reflect_dgrad_rowmap(int64_t B, int64_t H, int64_t W, int64_t pt,
+                                int64_t pb, int64_t pl, int64_t pr,
+                                int64_t KH, int64_t KW, bool trim,
+                                bool frame) {
+  TORCH_CHECK(B > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && pt >= 0 &&
+              pb >= 0 && pl >= 0 && pr >= 0, "reflect_dgrad_rowmap: sizes");
+  TORCH_CHECK(B * (H + pt + pb) * (W + pl + pr) < (1L << 24),
+              "reflect_dgrad_rowmap: a table for small shapes");
+  const ReflectOrder o =
+      reflect_order(B, H, W, pt, pb, pl, pr, KH, KW, frame, trim);
+  const int tiles = o.cstart[4];
+  auto out = at::empty({(long)tiles * BM, 10}, at::kInt);
+  int* t = out.data_ptr<int>();
+  for (int tile = 0; tile < tiles; ++tile)
+    for (int r = 0; r < BM; ++r, t += 10) {
+      const ReflectRow d = reflect_row(o, tile, r);
+      t[0] = d.ok; t[1] = d.b; t[2] = d.qh; t[3] = d.qw; t[4] = d.cls;
+      t[5] = d.taps.kh0; t[6] = d.taps.kh1;
+      t[7] = d.taps.kw0; t[8] = d.taps.kw1;
+      t[9] = (int)d.dst;
+    }
+  return out;
 }
 
 // convt dgrad: adjoint of the convt gather == strided conv_fwd of dy.
