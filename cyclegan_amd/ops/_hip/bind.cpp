@@ -70,16 +70,20 @@ std::vector<at::Tensor> persample_loss_bwd(at::Tensor, at::Tensor, at::Tensor,
                                            bool, bool, bool);
 at::Tensor persample_loss_const_bwd(at::Tensor, double, at::Tensor, bool);
 void adam_step_dev(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                   double, double, double);
+                   double, double, double, c10::optional<at::Tensor>);
 void adam_ema_step(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                   double, double, double, double, int64_t, double);
+                   double, double, double, double, int64_t, double,
+                   c10::optional<at::Tensor>);
 void adam_ema_step_dev(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                       at::Tensor, at::Tensor, double, double, double, double);
+                       at::Tensor, at::Tensor, double, double, double, double,
+                       c10::optional<at::Tensor>);
 void shadow_gather(at::Tensor, at::Tensor, at::Tensor);
+void shadow_cast(at::Tensor, at::Tensor);
+void shadow_transpose(at::Tensor, at::Tensor, at::Tensor, at::Tensor);
 void shadow_fold(at::Tensor, at::Tensor, at::Tensor);
 void fold_upconv_dw_into(at::Tensor, at::Tensor, bool, bool);
 void adam_step(at::Tensor, at::Tensor, at::Tensor, at::Tensor, double, double,
-               double, double, int64_t);
+               double, double, int64_t, c10::optional<at::Tensor>);
 at::Tensor augment_batch(at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
                          at::Tensor);
 at::Tensor pool_exchange(at::Tensor, at::Tensor, at::Tensor, at::Tensor);
@@ -146,12 +150,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("persample_loss_const_fwd", &cyg::persample_loss_const_fwd);
   m.def("persample_loss_bwd", &cyg::persample_loss_bwd);
   m.def("persample_loss_const_bwd", &cyg::persample_loss_const_bwd);
-  m.def("adam_step", &cyg::adam_step);
-  m.def("adam_step_dev", &cyg::adam_step_dev);
+  // trailing `shadow` (all four Adam steps): the bf16 mirror of p that the
+  // kernel also writes, bf16(p_new) at each element's own index; None: off
+  m.def("adam_step", &cyg::adam_step, py::arg("p"), py::arg("g"),
+        py::arg("m"), py::arg("v"), py::arg("lr"), py::arg("b1"),
+        py::arg("b2"), py::arg("eps"), py::arg("t"),
+        py::arg("shadow") = py::none());
+  m.def("adam_step_dev", &cyg::adam_step_dev, py::arg("p"), py::arg("g"),
+        py::arg("m"), py::arg("v"), py::arg("lr_t"), py::arg("b1"),
+        py::arg("b2"), py::arg("eps"), py::arg("shadow") = py::none());
   // Adam + weight EMA in one pass (p, m, v bitwise as the two above)
-  m.def("adam_ema_step", &cyg::adam_ema_step);
-  m.def("adam_ema_step_dev", &cyg::adam_ema_step_dev);
+  m.def("adam_ema_step", &cyg::adam_ema_step, py::arg("p"), py::arg("g"),
+        py::arg("m"), py::arg("v"), py::arg("ema"), py::arg("lr"),
+        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("t"),
+        py::arg("ema_decay"), py::arg("shadow") = py::none());
+  m.def("adam_ema_step_dev", &cyg::adam_ema_step_dev, py::arg("p"),
+        py::arg("g"), py::arg("m"), py::arg("v"), py::arg("ema"),
+        py::arg("lr_t"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
+        py::arg("ema_decay"), py::arg("shadow") = py::none());
   m.def("shadow_gather", &cyg::shadow_gather);
+  // mirror refresh outside the optimizer (fp32 masters -> bf16 mirror), and
+  // the index-free [Cout,taps,Cin] -> [Cin,taps,Cout] transposes of the
+  // dgrad forms over a per-layer table (host copy validated per call)
+  m.def("shadow_cast", &cyg::shadow_cast);
+  m.def("shadow_transpose", &cyg::shadow_transpose, py::arg("src"),
+        py::arg("table"), py::arg("table_dev"), py::arg("dst"));
   // resize-convolution: folded 4x4 forms from the 3x3 masters, and the
   // 4x4 weight gradient unfolded onto the 3x3 master's gradient block
   m.def("shadow_fold", &cyg::shadow_fold);

@@ -13,6 +13,7 @@ typedef __bf16 bf16r;
 typedef bf16r v8bf __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef short v8s __attribute__((ext_vector_type(8)));
+typedef short v4s __attribute__((ext_vector_type(4)));
 
 // raw bf16 <-> f32 (RNE via hardware conversion)
 DEV float b2f(short raw) {

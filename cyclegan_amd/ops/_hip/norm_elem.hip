@@ -679,28 +679,40 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m,
   p -= lr_t * mi / (sqrtf(vi) + eps);
 }
 
+// SHADOW (all Adam kernels): also store bf16(p_new) at the element's own
+// index of `shadow`, the mirror region of the shadow arena (ops.arena) —
+// the updated p is in a register, so the unpadded OHWI compute forms cost
+// 2 B/param here instead of a gather pass. p, m, v (and ema) are what the
+// !SHADOW instantiation writes, bit for bit (tests/test_adam_shadow_gpu.py).
+template <bool SHADOW>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                             float* __restrict__ m, float* __restrict__ v,
                             long n, float lr_t, float b1, float b2,
-                            float eps) {
+                            float eps, short* __restrict__ shadow) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride)
+  for (; i < n; i += stride) {
     adam_elem(p[i], g[i], m[i], v[i], lr_t, b1, b2, eps);
+    if (SHADOW) shadow[i] = f2b(p[i]);
+  }
 }
 
 // graph-capture variant: lr_t read from device memory so a captured step
 // picks up the per-step bias correction the host writes before each replay
+template <bool SHADOW>
 __global__ void adam_kernel_dev(float* __restrict__ p,
                                 const float* __restrict__ g,
                                 float* __restrict__ m, float* __restrict__ v,
                                 long n, const float* __restrict__ lr_t_ptr,
-                                float b1, float b2, float eps) {
+                                float b1, float b2, float eps,
+                                short* __restrict__ shadow) {
   const float lr_t = *lr_t_ptr;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride)
+  for (; i < n; i += stride) {
     adam_elem(p[i], g[i], m[i], v[i], lr_t, b1, b2, eps);
+    if (SHADOW) shadow[i] = f2b(p[i]);
+  }
 }
 
 // ---- Adam + exponential moving average of the weights, one pass ----
@@ -723,13 +735,16 @@ __device__ __forceinline__ void adam_ema_elem(float& p, float g, float& m,
 // pointers 16-byte aligned, checked by the host) and a scalar tail of
 // n%4; !VEC: scalar throughout, for views at an odd storage offset.
 // LR_DEV: lr_t read from device memory (capture-safe, as adam_kernel_dev).
-template <bool VEC, bool LR_DEV>
+// SHADOW: as above; the VEC path stores its four bf16 as one 8-byte word
+// (shadow 8-byte aligned, checked by the host).
+template <bool VEC, bool LR_DEV, bool SHADOW>
 __global__ void adam_ema_kernel(float* __restrict__ p,
                                 const float* __restrict__ g,
                                 float* __restrict__ m, float* __restrict__ v,
                                 float* __restrict__ ema, long n, float lr_imm,
                                 const float* __restrict__ lr_t_ptr, float b1,
-                                float b2, float eps, float d, float omd) {
+                                float b2, float eps, float d, float omd,
+                                short* __restrict__ shadow) {
   const float lr_t = LR_DEV ? *lr_t_ptr : lr_imm;
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
@@ -751,11 +766,17 @@ __global__ void adam_ema_kernel(float* __restrict__ p,
       v4[i] = vi;
       p4[i] = pi;
       e4[i] = ei;
+      if (SHADOW) {
+        v4s s = {f2b(pi.x), f2b(pi.y), f2b(pi.z), f2b(pi.w)};
+        reinterpret_cast<v4s*>(shadow)[i] = s;
+      }
     }
     done = n4 << 2;
   }
-  for (long i = done + tid; i < n; i += stride)
+  for (long i = done + tid; i < n; i += stride) {
     adam_ema_elem(p[i], g[i], m[i], v[i], ema[i], lr_t, b1, b2, eps, d, omd);
+    if (SHADOW) shadow[i] = f2b(p[i]);
+  }
 }
 
 // ================= host wrappers =================
@@ -1146,45 +1167,71 @@ at::Tensor persample_loss_const_bwd(at::Tensor yp, double cconst,
   return gp;
 }
 
+// The optional mirror (SHADOW kernels): bf16, contiguous, on p's device, at
+// least p.numel() long. Returns its pointer, or nullptr when absent.
+static short* adam_shadow_ptr(const c10::optional<at::Tensor>& shadow,
+                              const at::Tensor& p) {
+  if (!shadow.has_value()) return nullptr;
+  const at::Tensor& s = *shadow;
+  TORCH_CHECK(s.is_cuda() && s.device() == p.device() &&
+                  s.scalar_type() == at::kBFloat16 && s.is_contiguous() &&
+                  s.numel() >= p.numel(),
+              "adam: shadow must be a contiguous bf16 tensor on the "
+              "parameters' device, at least as long as they are");
+  return (short*)s.mutable_data_ptr();
+}
+
 void adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
-               double lr, double b1, double b2, double eps, int64_t t) {
+               double lr, double b1, double b2, double eps, int64_t t,
+               c10::optional<at::Tensor> shadow) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat);
   long n = p.numel();
+  short* sp = adam_shadow_ptr(shadow, p);
   // TF formula: lr_t = lr*sqrt(1-b2^t)/(1-b1^t); eps beside sqrt(v)
   double lr_t = lr * std::sqrt(1.0 - std::pow(b2, (double)t)) /
                 (1.0 - std::pow(b1, (double)t));
   int blocks = (int)std::min<long>(2048, (n + 255) / 256);
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     (float*)p.mutable_data_ptr(),
-                     (const float*)g.const_data_ptr(),
-                     (float*)m.mutable_data_ptr(),
-                     (float*)v.mutable_data_ptr(), n, (float)lr_t, (float)b1,
-                     (float)b2, (float)eps);
+#define CYG_ADAM(SH)                                                        \
+  hipLaunchKernelGGL(adam_kernel<SH>, dim3(blocks), dim3(256), 0,           \
+                     at::cuda::getCurrentCUDAStream(),                      \
+                     (float*)p.mutable_data_ptr(),                          \
+                     (const float*)g.const_data_ptr(),                      \
+                     (float*)m.mutable_data_ptr(),                          \
+                     (float*)v.mutable_data_ptr(), n, (float)lr_t,          \
+                     (float)b1, (float)b2, (float)eps, sp)
+  if (sp) CYG_ADAM(true); else CYG_ADAM(false);
+#undef CYG_ADAM
 }
 
 void adam_step_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
-                   at::Tensor lr_t, double b1, double b2, double eps) {
+                   at::Tensor lr_t, double b1, double b2, double eps,
+                   c10::optional<at::Tensor> shadow) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat);
   TORCH_CHECK(lr_t.is_cuda() && lr_t.scalar_type() == at::kFloat);
   long n = p.numel();
+  short* sp = adam_shadow_ptr(shadow, p);
   int blocks = (int)std::min<long>(2048, (n + 255) / 256);
-  hipLaunchKernelGGL(adam_kernel_dev, dim3(blocks), dim3(256), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     (float*)p.mutable_data_ptr(),
-                     (const float*)g.const_data_ptr(),
-                     (float*)m.mutable_data_ptr(),
-                     (float*)v.mutable_data_ptr(), n,
-                     (const float*)lr_t.const_data_ptr(), (float)b1,
-                     (float)b2, (float)eps);
+#define CYG_ADAM_DEV(SH)                                                    \
+  hipLaunchKernelGGL(adam_kernel_dev<SH>, dim3(blocks), dim3(256), 0,       \
+                     at::cuda::getCurrentCUDAStream(),                      \
+                     (float*)p.mutable_data_ptr(),                          \
+                     (const float*)g.const_data_ptr(),                      \
+                     (float*)m.mutable_data_ptr(),                          \
+                     (float*)v.mutable_data_ptr(), n,                       \
+                     (const float*)lr_t.const_data_ptr(), (float)b1,        \
+                     (float)b2, (float)eps, sp)
+  if (sp) CYG_ADAM_DEV(true); else CYG_ADAM_DEV(false);
+#undef CYG_ADAM_DEV
 }
 
 // shared by adam_ema_step / adam_ema_step_dev: checks, path choice, launch
 static void adam_ema_launch(at::Tensor& p, at::Tensor& g, at::Tensor& m,
                             at::Tensor& v, at::Tensor& ema, float lr_imm,
                             const float* lr_t_ptr, double b1, double b2,
-                            double eps, double ema_decay) {
+                            double eps, double ema_decay,
+                            const c10::optional<at::Tensor>& shadow) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat);
+  short* sp = adam_shadow_ptr(shadow, p);
   for (const at::Tensor* t : {&p, &g, &m, &v, &ema}) {
     TORCH_CHECK(t->scalar_type() == at::kFloat, "adam_ema: fp32 only");
     TORCH_CHECK(t->numel() == p.numel(), "adam_ema: numel mismatch");
@@ -1205,7 +1252,8 @@ static void adam_ema_launch(at::Tensor& p, at::Tensor& g, at::Tensor& m,
                reinterpret_cast<uintptr_t>(gp) |
                reinterpret_cast<uintptr_t>(mp) |
                reinterpret_cast<uintptr_t>(vp) |
-               reinterpret_cast<uintptr_t>(ep)) & 15) == 0;
+               reinterpret_cast<uintptr_t>(ep)) & 15) == 0 &&
+             (reinterpret_cast<uintptr_t>(sp) & 7) == 0;
   // constants of the run: 1-d in double, then cast (a captured graph
   // bakes both in)
   float d = (float)ema_decay, omd = (float)(1.0 - ema_decay);
@@ -1213,9 +1261,18 @@ static void adam_ema_launch(at::Tensor& p, at::Tensor& g, at::Tensor& m,
   int blocks = (int)std::min<long>(2048, (work + 255) / 256);
   auto stream = at::cuda::getCurrentCUDAStream();
 #define CYG_ADAM_EMA(VEC, LRD)                                              \
-  hipLaunchKernelGGL((adam_ema_kernel<VEC, LRD>), dim3(blocks), dim3(256),  \
-                     0, stream, pp, gp, mp, vp, ep, n, lr_imm, lr_t_ptr,    \
-                     (float)b1, (float)b2, (float)eps, d, omd)
+  do {                                                                      \
+    if (sp)                                                                 \
+      hipLaunchKernelGGL((adam_ema_kernel<VEC, LRD, true>), dim3(blocks),   \
+                         dim3(256), 0, stream, pp, gp, mp, vp, ep, n,       \
+                         lr_imm, lr_t_ptr, (float)b1, (float)b2,            \
+                         (float)eps, d, omd, sp);                           \
+    else                                                                    \
+      hipLaunchKernelGGL((adam_ema_kernel<VEC, LRD, false>), dim3(blocks),  \
+                         dim3(256), 0, stream, pp, gp, mp, vp, ep, n,       \
+                         lr_imm, lr_t_ptr, (float)b1, (float)b2,            \
+                         (float)eps, d, omd, sp);                           \
+  } while (0)
   if (lr_t_ptr) {
     if (vec) CYG_ADAM_EMA(true, true); else CYG_ADAM_EMA(false, true);
   } else {
@@ -1226,21 +1283,23 @@ static void adam_ema_launch(at::Tensor& p, at::Tensor& g, at::Tensor& m,
 
 void adam_ema_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                    at::Tensor ema, double lr, double b1, double b2,
-                   double eps, int64_t t, double ema_decay) {
+                   double eps, int64_t t, double ema_decay,
+                   c10::optional<at::Tensor> shadow) {
   // same host arithmetic as adam_step: the immediate must be bit-equal
   double lr_t = lr * std::sqrt(1.0 - std::pow(b2, (double)t)) /
                 (1.0 - std::pow(b1, (double)t));
   adam_ema_launch(p, g, m, v, ema, (float)lr_t, nullptr, b1, b2, eps,
-                  ema_decay);
+                  ema_decay, shadow);
 }
 
 void adam_ema_step_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                        at::Tensor ema, at::Tensor lr_t, double b1, double b2,
-                       double eps, double ema_decay) {
+                       double eps, double ema_decay,
+                       c10::optional<at::Tensor> shadow) {
   TORCH_CHECK(lr_t.is_cuda() && lr_t.scalar_type() == at::kFloat &&
               lr_t.numel() == 1 && lr_t.device() == p.device());
   adam_ema_launch(p, g, m, v, ema, 0.f, (const float*)lr_t.const_data_ptr(),
-                  b1, b2, eps, ema_decay);
+                  b1, b2, eps, ema_decay, shadow);
 }
 
 }  // namespace cyg

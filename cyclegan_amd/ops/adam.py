@@ -14,8 +14,12 @@ tiny but we match TF for parity.
 
 On MI355X this is ONE kernel per model over the flat buffers (the whole
 generator is a single 11.4M-element update — zero per-tensor launch
-overhead), which also refreshes nothing else: bf16 shadow weights recast
-lazily via the version counter (ops.shadow).
+overhead). Given a ``shadow`` (the mirror of the group's shadow arena,
+ops.arena) the same kernel also stores bf16(p_new) there, 2 B/param more,
+which is the unpadded OHWI compute form of every conv weight; p, m, v and
+ema are bitwise what they are without it. Without one it refreshes
+nothing else: bf16 shadow weights recast lazily via the version counter
+(ops.shadow).
 
 Two optional parts of the CycleGAN recipe live in the same step:
 
@@ -60,6 +64,10 @@ class FusedAdam:
         # per-step bias correction written by advance_lr() before replay
         self.graph_mode = False
         self._lr_t_dev = None
+        # bf16 mirror of flat_param the HIP kernels also write (the arena
+        # sets it; None: off), and whether the last step() wrote it
+        self.shadow = None
+        self.wrote_shadow = False
 
     def _lr_t(self) -> float:
         return (self.lr * self.lr_scale * math.sqrt(1 - self.b2 ** self.t)
@@ -93,27 +101,31 @@ class FusedAdam:
 
     @torch.no_grad()
     def step(self):
+        self.wrote_shadow = False
         if self.graph_mode:
+            self.wrote_shadow = self.shadow is not None
             # t/lr_t advanced by advance_lr(); capture-safe kernel
             if self.ema is not None:
                 backend.ext().adam_ema_step_dev(
                     self.p, self.g, self.m, self.v, self.ema, self._lr_t_dev,
-                    self.b1, self.b2, self.eps, self.ema_decay)
+                    self.b1, self.b2, self.eps, self.ema_decay, self.shadow)
                 return
             backend.ext().adam_step_dev(self.p, self.g, self.m, self.v,
                                         self._lr_t_dev, self.b1, self.b2,
-                                        self.eps)
+                                        self.eps, self.shadow)
             return
         self.t += 1
         if backend.use_hip(self.p):
             lr = self.lr * self.lr_scale
+            self.wrote_shadow = self.shadow is not None
             if self.ema is not None:
                 backend.ext().adam_ema_step(
                     self.p, self.g, self.m, self.v, self.ema, lr, self.b1,
-                    self.b2, self.eps, self.t, self.ema_decay)
+                    self.b2, self.eps, self.t, self.ema_decay, self.shadow)
             else:
                 backend.ext().adam_step(self.p, self.g, self.m, self.v,
-                                        lr, self.b1, self.b2, self.eps, self.t)
+                                        lr, self.b1, self.b2, self.eps, self.t,
+                                        self.shadow)
             # the raw kernel bypasses the dispatcher, so the in-place update
             # does not bump the version counter that invalidates the bf16
             # shadow-weight caches (ops.shadow) — bump it explicitly, or

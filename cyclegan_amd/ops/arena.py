@@ -1,5 +1,5 @@
-"""Shadow arena: all bf16 compute-weight forms of a model group in ONE
-flat buffer, refreshed by ONE gather kernel per optimizer step.
+"""Shadow arena: all bf16 compute-weight forms of a model group in a few
+flat buffers, refreshed once per optimizer step.
 
 Masters live in a group's flat fp32 buffer (parallel.flat.FlatParamGroup).
 Every conv needs derived bf16 forms — padded OHWI for forward, padded
@@ -16,19 +16,69 @@ live in a second segment (fold_buf) with an [n,4] index table, filled by
 shadow_fold right after the gather; a model without such layers has an
 empty segment and launches only the gather.
 
+Most of the bytes need no index map. On the GPU (CYG_NO_ADAM_SHADOW=1
+restores the full gather) the arena keeps a MIRROR, the bf16 image of the
+whole flat buffer, which the fused Adam kernels write while p_new is in a
+register (FusedAdam.shadow):
+
+- a conv weight's OHWI form is a VIEW into the mirror when no dimension is
+  padded and its flat offset is a multiple of 8 elements (the glds weight
+  loads need 16-byte alignment);
+- its channel-transposed form comes from shadow_transpose, one launch per
+  group over a small per-layer table, when Cout and Cin are multiples of 8
+  as well;
+- everything else (padded stems and heads, the packed head form, biases,
+  odd offsets) stays on the gather, whose index map shrinks to that
+  remainder. The fold segment is as it was.
+
+refresh() casts the mirror itself unless the caller says Adam has just
+written it, so masters changed any other way give valid forms too.
+
 GPU-only: CPU paths keep the version-keyed caches in ops.shadow (fp32
 compute needs no casting there).
 """
 
 from __future__ import annotations
 
-from typing import Dict, List, Tuple
+import os
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import backend
 
 _PAD = 8  # glds kernels need channel dims >= 8
+
+# shadow.hip: columns of a transpose-table row, tile edge of its blocks
+_ST_COLS = 8
+_ST_T = 64
+
+
+def mirror_enabled() -> bool:
+    """CYG_NO_ADAM_SHADOW=1 turns the mirror off (every form from the full
+    gather again); read when an arena is built."""
+    return os.environ.get("CYG_NO_ADAM_SHADOW") != "1"
+
+
+def mirror_view_ok(base: int, shape) -> bool:
+    """The OHWI form may be a view into the mirror: nothing padded, 16-byte
+    aligned."""
+    O, _, _, I = shape
+    return O >= _PAD and I >= _PAD and base % 8 == 0
+
+
+def transpose_ok(base: int, shape) -> bool:
+    """shadow_transpose can build the channel-transposed form: whole
+    16-byte words on both sides."""
+    O, _, _, I = shape
+    return O % 8 == 0 and I % 8 == 0 and base % 8 == 0
+
+
+def transpose_row(src: int, dst: int, shape, first_block: int) -> List[int]:
+    """One table row of shadow_transpose, and the blocks it takes."""
+    O, KH, KW, I = shape
+    tci, tco = -(-I // _ST_T), -(-O // _ST_T)
+    return [src, dst, O, KH * KW, I, first_block, tci, tco]
 
 
 def _conv_like(m: torch.nn.Module) -> bool:
@@ -144,11 +194,17 @@ def _idx_packb(base: int, n: int) -> torch.Tensor:
 
 
 class ShadowArena:
-    """Builds and refreshes the arena for one FlatParamGroup + its module."""
+    """Builds and refreshes the arena for one FlatParamGroup + its module.
 
-    def __init__(self, group, module: torch.nn.Module):
+    mirror: None takes the default (on for a device group unless
+    CYG_NO_ADAM_SHADOW=1); False is the full gather."""
+
+    def __init__(self, group, module: torch.nn.Module,
+                 mirror: Optional[bool] = None):
         self.group = group
         dev = group.flat_param.device
+        if mirror is None:
+            mirror = group.flat_param.is_cuda and mirror_enabled()
         off = {p: o for p, (o, _) in zip(group.params, group._offsets)}
 
         pieces: List[torch.Tensor] = []           # int32 index chunks (cpu)
@@ -158,6 +214,12 @@ class ShadowArena:
         fpieces: List[torch.Tensor] = []
         fplan: List[Tuple[torch.nn.Parameter, str, Tuple[int, ...], int]] = []
         ftotal = 0
+        # mirror views (start = flat offset) and transposed forms (start in
+        # tbuf, one table row each)
+        vplan: List[Tuple[torch.nn.Parameter, str, Tuple[int, ...], int]] = []
+        tplan: List[Tuple[torch.nn.Parameter, str, Tuple[int, ...], int]] = []
+        trows: List[List[int]] = []
+        ttotal = tblocks = 0
         for m in module.modules():
             if _upconv_like(m):
                 w = m.weight
@@ -180,8 +242,22 @@ class ShadowArena:
                 if not isinstance(m.padding, str) else (0,) * 4))
             if packed:
                 forms.append(("packp", _idx_packp))
+            shape = tuple(w.shape)
+            O, KH, KW, I = shape
             for name, fn in forms:
-                idx = fn(off[w], tuple(w.shape))
+                if mirror and name in ("p", "plain") \
+                        and mirror_view_ok(off[w], shape):
+                    vplan.append((w, name, shape, off[w]))
+                    continue
+                if mirror and name in ("tp", "t") \
+                        and transpose_ok(off[w], shape):
+                    row = transpose_row(off[w], ttotal, shape, tblocks)
+                    trows.append(row)
+                    tplan.append((w, name, (I, KH, KW, O), ttotal))
+                    ttotal += w.numel()
+                    tblocks += row[3] * row[6] * row[7]
+                    continue
+                idx = fn(off[w], shape)
                 pieces.append(idx.reshape(-1))
                 plan.append((w, name, tuple(idx.shape), total))
                 total += idx.numel()
@@ -211,26 +287,53 @@ class ShadowArena:
         self.fold_buf = torch.empty(self.fold_idx.shape[0],
                                     dtype=torch.bfloat16, device=dev)
 
-        # per-(master, form) shaped views into the arena
+        # mirror (flat length rounded up to whole 16-byte words), the
+        # transposed forms and their table, on the host and on the device
+        self.mirror = None
+        if mirror:
+            n = group.flat_param.numel()
+            self.mirror = torch.zeros(n + (-n) % 8, dtype=torch.bfloat16,
+                                      device=dev)
+        self.tbuf = torch.empty(ttotal, dtype=torch.bfloat16, device=dev)
+        self.ttable = torch.tensor(trows, dtype=torch.int32).reshape(
+            -1, _ST_COLS)
+        self.ttable_dev = self.ttable.to(dev)
+
+        # per-(master, form) shaped views into the arena, and where each
+        # one comes from: "mirror", "transpose", "gather" or "fold"
         self.views: Dict[Tuple[int, str], torch.Tensor] = {}
         self._by_param: Dict[torch.Tensor, Dict[str, torch.Tensor]] = {}
-        for p, name, shape, start in plan:
-            v = self.buf[start:start + int(torch.tensor(shape).prod())].view(shape)
-            self._by_param.setdefault(p, {})[name] = v
-        for p, name, shape, start in fplan:
-            v = self.fold_buf[start:start + int(torch.tensor(shape).prod())]
-            self._by_param.setdefault(p, {})[name] = v.view(shape)
+        self.source: Dict[torch.Tensor, Dict[str, str]] = {}
+        for kind, store, entries in (("gather", self.buf, plan),
+                                     ("fold", self.fold_buf, fplan),
+                                     ("mirror", self.mirror, vplan),
+                                     ("transpose", self.tbuf, tplan)):
+            for p, name, shape, start in entries:
+                v = store[start:start + int(torch.tensor(shape).prod())]
+                self._by_param.setdefault(p, {})[name] = v.view(shape)
+                self.source.setdefault(p, {})[name] = kind
 
         self.refresh()
 
-    def refresh(self):
-        """One gather kernel: flat fp32 masters -> every bf16 form; one
-        fold kernel more when the model has resize-convolution layers."""
+    def refresh(self, mirror_fresh: bool = False):
+        """Masters -> every bf16 form. With the mirror: a cast pass fills
+        it unless ``mirror_fresh`` (the Adam step on this stream has just
+        written it), one transpose launch builds the dgrad forms from it,
+        and the gather does the irregular remainder. Without: one gather
+        for everything. One fold kernel more when the model has
+        resize-convolution layers."""
+        ext = backend.ext()
+        if self.mirror is not None:
+            if not mirror_fresh:
+                ext.shadow_cast(self.group.flat_param, self.mirror)
+            if self.ttable.shape[0]:
+                ext.shadow_transpose(self.mirror, self.ttable,
+                                     self.ttable_dev, self.tbuf)
         if self.idx.numel():
-            backend.ext().shadow_gather(self.group.flat_param, self.idx, self.buf)
+            ext.shadow_gather(self.group.flat_param, self.idx, self.buf)
         if self.fold_idx.numel():
-            backend.ext().shadow_fold(self.group.flat_param, self.fold_idx,
-                                      self.fold_buf)
+            ext.shadow_fold(self.group.flat_param, self.fold_idx,
+                            self.fold_buf)
 
     def forms_of(self, p: torch.Tensor):
         return self._by_param.get(p)

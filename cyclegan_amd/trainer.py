@@ -106,8 +106,9 @@ class CycleGAN:
             for name, g in self.groups.items()}
         self.sync = GradSync(ctx, timing=getattr(args, "verbose", 1) == 2)
 
-        # shadow arenas: every bf16 compute form of a group refreshed by
-        # ONE gather kernel after each optimizer step (ops/arena.py)
+        # shadow arenas: every bf16 compute form of a group, refreshed
+        # after each optimizer step (ops/arena.py). Adam writes the arena's
+        # mirror itself; the refresh builds the rest from it
         self.arenas = {}
         if (self.device.type == "cuda"
                 and self.compute_dtype == torch.bfloat16
@@ -118,6 +119,7 @@ class CycleGAN:
                 a = ShadowArena(self.groups[name], getattr(self, name))
                 _shadow.register_arena(a)
                 self.arenas[name] = a
+                self.optimizers[name].shadow = a.mirror
 
         # image history pools (fake x, fake y): built at the first step,
         # when the image shape is known; every rank keeps its own
@@ -144,9 +146,13 @@ class CycleGAN:
         # lazily-captured hip-graph step (main.py at N=1)
         self.graphed = None
 
-    def _refresh_shadows(self):
-        for a in self.arenas.values():
-            a.refresh()
+    def _refresh_shadows(self, after_adam: bool = False):
+        """after_adam: called right behind the optimizer steps on the same
+        stream, so a mirror that Adam wrote is current; anywhere else the
+        arena casts it from the masters itself."""
+        for name, a in self.arenas.items():
+            a.refresh(mirror_fresh=after_adam
+                      and self.optimizers[name].wrote_shadow)
 
     def _snapshot_state(self):
         """Everything a train step may touch, for _restore_state: flat
@@ -453,7 +459,7 @@ class CycleGAN:
             opt.step()
         for g in self.groups.values():
             g.bump_versions()  # invalidate bf16 shadow caches (see flat.py)
-        self._refresh_shadows()
+        self._refresh_shadows(after_adam=True)
         if self._fp8 and roll_amax:
             from .ops import fp8_state
             fp8_state.roll()  # delayed-scaling amax: prev <- cur
